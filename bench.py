@@ -21,6 +21,18 @@ The JSON line also carries:
   cpu_baseline — the CPU digest+dedup stage (oracle/cpu_baseline.c: official
                  BLAKE3 C with AVX-512 dispatch, pthreads, stream-order dedup)
                  on a bounded sample of the same layer, rank 0 at N=1 only.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+headline figure needs: set up, warm up, time the N steps, print the line.  Its
+roofline entries come from the timed steps' own HIP events.  Everything that
+takes work of its own -- the CPU baseline, the PCIe-inclusive rates, the
+independent digest check past 4 GiB, the probe-only roofline and the
+ChunkDictPath file of the dict workloads, C5's host Merge, the C1 / C3 /
+C5-1000 / --packs sub-entries (child runs), and the N > 1 extras -- runs with
+`--full` only.
+
+`--dump-outputs DIR` writes the result table of the last timed step (what the
+caller of the timed path receives) as DIR/<name>.npy; see dump_outputs.
 """
 from __future__ import annotations
 
@@ -874,6 +886,42 @@ def node_e2e(torch, dist, nydus_gpu, buf, wl, stride, device, backend, sample_by
             "bound": "one PCIe Gen5 x16 link per GPU (~50-55 GB/s H2D) and the host DRAM they share"}
 
 
+DUMP_MAX_BYTES = 48 * MiB  # of the 64 MB a dump may take
+DUMP_SEED = 0xD0E5
+
+
+def dump_outputs(where, res, layer_stats=None, rank=0):
+    """`--dump-outputs DIR`: the last timed step's result table (the records the
+    caller of the timed path gets back in host memory), one array per field as
+    DIR/<field>.npy: `digest` (rows x 32 bytes) in float32, the record's other
+    fields in float64 (exact: every value is below 2^53), `rows` = the table
+    rows they were taken from.  A table above DUMP_MAX_BYTES is sampled: a
+    fixed (seeded) sorted choice of rows, the same on every run.  The
+    multi-layer path's per-layer stats go to `layer_stats` (layers x fields of
+    LAYER_STATS_DTYPE).  N > 1: every rank writes its own table, ranks above 0
+    as <field>_rank<r>.npy.  The inputs are seeded, so two builds given the
+    same arguments can be compared array for array."""
+    os.makedirs(where, exist_ok=True)
+    n = len(res)
+    scalars = [f for f in res.dtype.names if f != "digest"]
+    per_row = 32 * 4 + 8 * (len(scalars) + 1)
+    keep = DUMP_MAX_BYTES // per_row
+    rows = np.arange(n, dtype=np.int64)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    sfx = f"_rank{rank}" if rank else ""
+    out = {"rows": rows.astype(np.float64), "digest": res["digest"][rows].astype(np.float32)}
+    for f in scalars:
+        out[f] = res[f][rows].astype(np.float64)
+    if layer_stats is not None:
+        out["layer_stats"] = np.stack([layer_stats[f].astype(np.float64)
+                                       for f in layer_stats.dtype.names], 1)
+    for name, a in out.items():
+        np.save(os.path.join(where, f"{name}{sfx}.npy"), a)
+    return {"dir": where, "rows": int(len(rows)), "of": n,
+            "bytes": int(sum(a.nbytes for a in out.values())), "arrays": sorted(out)}
+
+
 SUB_KEYS = ("value", "unit", "ms_per_step", "steps", "warmup", "config", "stage_ms", "roofline",
             "cpu_baseline", "speedup_vs_cpu", "speedup_vs_cpu_single_stream", "dict",
             "probe_roofline", "merge", "decisions", "digest_check_past_4gib", "n_gpus", "sharded_dict",
@@ -901,7 +949,7 @@ def child_line(cmd, timeout_s, env=None):
 
 
 def sub_entries(args):
-    """N = 1: driver-timed evidence beside the C2 headline: C1 (the small
+    """N = 1, --full: driver-timed evidence beside the C2 headline: C1 (the small
     alpine-like layer, with its host path), and for the dict paths (VERDICT r3
     item 5) C3 (sha256, 200M-entry dict in HBM, probe_roofline)
     and C5-1000 (1000 x 64 MiB layers, 64 KiB chunks, pool dict, one
@@ -920,7 +968,7 @@ def sub_entries(args):
         # steps: a step is ~0.06 ms
         steps = args.sub_steps * 10 if wl == "c1" else args.sub_steps
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps",
-               str(steps), "--no-sub", "--settle-s", "1.0"] + ([] if wl == "c1" else ["--no-e2e"])
+               str(steps), "--full", "--no-sub", "--settle-s", "1.0"] + ([] if wl == "c1" else ["--no-e2e"])
         out[key] = child_line(cmd, 420)
     return out
 
@@ -1009,7 +1057,7 @@ def c4_entry(world, layers, steps, backend="nccl", timeout_s=420):
     for k in DIST_ENV:
         env.pop(k, None)
     cmd = self_launch_cmd([], world, free_port()) + ["--gpus", str(world), "--workload", "c4",
-           "--steps", str(steps), "--warmup", "15", "--no-sharded-extra", "--no-node-extra",
+           "--steps", str(steps), "--warmup", "15", "--full", "--no-sharded-extra", "--no-node-extra",
            "--no-e2e", "--no-c4", "--c4-layers", str(layers), "--dist-backend", backend]
     return child_line(cmd, timeout_s, env=env)
 
@@ -1786,7 +1834,15 @@ def rank_check(args, dist, world, rank, local, backend, torch, group=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baseline, PCIe-inclusive "
+                         "rates, the digest check past 4 GiB, the dict workloads' probe roofline and "
+                         "ChunkDictPath file, C5's Merge, the sub-entries (child runs) and the N > 1 "
+                         "extras; the --no-* options below then leave single ones out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's result table as DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--settle-s", type=float, default=1.0,
                     help="after the W warmup steps, more untimed steps until the warm-up has "
                          "lasted this long (GPU clock ramp); 0 = W steps only")
@@ -1852,6 +1908,8 @@ def main():
     ap.add_argument("--node", default="", help="comma list of devices: one process drives them "
                     "through ngpu_node_* (a device may repeat: one-GPU rehearsal); see node_bench")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
     rc = maybe_self_launch(args, sys.argv[1:])
     if rc is not None:
         raise SystemExit(rc)
@@ -1963,13 +2021,13 @@ def main():
         torch.cuda.synchronize()
         build_s = time.perf_counter() - t0
         probe = None
-        if not wl.get("sharded") and args.probe_queries:
+        if args.full and not wl.get("sharded") and args.probe_queries:
             probe = probe_bench(torch, nydus_gpu, eng, dd, args.probe_queries, build_s)
         dict_host = None
-        if wl.get("merge") and world == 1:  # the C5 Merge needs the dict bootstrap
+        if args.full and wl.get("merge") and world == 1:  # the C5 Merge needs the dict bootstrap
             dict_host = (dd.cpu().numpy(), us.cpu().numpy(), bl.cpu().numpy(), ix.cpu().numpy())
         dict_file = None
-        if wl.get("dict_file") and not args.no_dict_file and rank == 0:
+        if args.full and wl.get("dict_file") and not args.no_dict_file and rank == 0:
             # ChunkDictPath itself: the same m records as a
             # RAFS v6 bootstrap on disk, opened through ngpu_dict_open (read,
             # parse, H2D, build); that dict then serves the timed steps
@@ -2081,9 +2139,15 @@ def main():
         extra["dict"]["dict_hits"] = int(kinds[2])
         assert kinds[2] >= extra["dict"]["expected_dict_hits"] * 0.99, (kinds, extra)
     extra["decisions"] = {"NEW": int(kinds[0]), "INTRA": int(kinds[1]), "DICT": int(kinds[2])}
-    if buf.numel() > (1 << 32) and rank == 0 and not no_load:  # digests past 2^32 (independent C/OpenSSL)
+    if args.dump_outputs:
+        lstats = None
+        if not (sdict is None and n_layers == 1):  # the multi-layer call's per-layer stats
+            lstats = d_lstats.cpu().numpy().view(nydus_gpu.LAYER_STATS_DTYPE)
+        extra["dump_outputs"] = dump_outputs(args.dump_outputs, res, lstats, rank)
+    if args.full and buf.numel() > (1 << 32) and rank == 0 and not no_load:
+        # digests past 2^32 (independent C/OpenSSL)
         extra["digest_check_past_4gib"] = check_high_digests(buf, ch, res, wl["digester"])
-    if wl.get("merge") and world == 1 and rank == 0:
+    if args.full and wl.get("merge") and world == 1 and rank == 0:
         extra["merge"] = merge_extra(nydus_gpu, ch, res, n_layers, per_layer, wl["chunk"], dict_host)
 
     timings = [eng.timing_at(b) for b in range(min(args.steps, 64))]
@@ -2197,9 +2261,10 @@ def main():
                                      "waves per SIMD"}
 
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e and not wl.get("dict_entries") and stride:
+    want_e2e = args.full and rank == 0 and world == 1 and not args.no_e2e
+    if want_e2e and not wl.get("dict_entries") and stride:
         e2e = end_to_end(torch, nydus_gpu, buf, wl, stride, local, sample_bytes=args.e2e_mib << 20)
-    elif rank == 0 and world == 1 and not args.no_e2e and wl.get("tar"):
+    elif want_e2e and wl.get("tar"):
         e2e = tar_host_path(nydus_gpu, tar, wl, local, file_bytes)
 
     roof["traffic"], roof["traffic_source"] = pmc_traffic(args.pmc_json, args.workload, roof["kernel"])
@@ -2207,7 +2272,7 @@ def main():
                  comp if wl["digester"] == "blake3" else 0)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # all the CPU the process may use: the CPUs of its affinity (`nproc`),
         # capped at its cgroup CPU quota when one is set -- on the GPU box
         # `nproc` shows 256 CPUs under a 16-core quota, and 256 threads thrash
@@ -2258,10 +2323,11 @@ def main():
     dog = None
     printed = [False]
     print_mu = __import__("threading").Lock()  # the line is printed once: here or by the watchdog
-    sharded_extra = dist and sdict is None and n_layers == 1 and not args.no_sharded_extra
-    node_pcie = dist and stride and not wl.get("dict_entries") and not wl.get("pool") and not args.no_e2e
-    node_cabi = dist and stride and not wl.get("dict_entries") and not wl.get("pool") and not args.no_node_extra
-    c4x = dist and args.workload == "c2" and not args.no_c4
+    extras = dist if args.full else None  # the N > 1 extras
+    sharded_extra = extras and sdict is None and n_layers == 1 and not args.no_sharded_extra
+    node_pcie = extras and stride and not wl.get("dict_entries") and not wl.get("pool") and not args.no_e2e
+    node_cabi = extras and stride and not wl.get("dict_entries") and not wl.get("pool") and not args.no_node_extra
+    c4x = extras and args.workload == "c2" and not args.no_c4
     if sharded_extra or node_pcie or node_cabi or c4x:
         # the headline is already measured; a watchdog keeps a stuck collective
         # (here, or in the closing barrier after a rank failed in here) from
@@ -2309,7 +2375,7 @@ def main():
                                       args.dist_backend)
             except Exception as ex:  # reported, never fatal to the headline line
                 line["c4"] = {"error": f"{type(ex).__name__}: {ex}"[:300]}
-    if rank == 0 and world == 1 and args.workload == "c2" and not args.no_sub:
+    if args.full and rank == 0 and world == 1 and args.workload == "c2" and not args.no_sub:
         line.update(sub_entries(args))
     mg = None
     if rank == 0 and dist:

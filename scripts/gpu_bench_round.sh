@@ -11,13 +11,13 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$ROOT"
 ok() { local rc=$1 what=$2; echo "$what rc=$rc"; if [ "$rc" -ne 0 ]; then echo "stopping after $what"; exit "$rc"; fi; }
-timeout -k 10 600 python3 bench.py > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+timeout -k 10 600 python3 bench.py --full > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
 ok $? bench_c2
 tail -c 3000 "$OUT/bench_c2.json"
-timeout -k 10 300 python3 bench.py --workload c1 --steps 200 --warmup 20 > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err"
+timeout -k 10 300 python3 bench.py --full --workload c1 --steps 200 --warmup 20 > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err"
 ok $? bench_c1
 for W in "$@"; do
-  timeout -k 10 600 python3 bench.py --workload $W --no-e2e > "$OUT/bench_$W.json" 2> "$OUT/bench_$W.err"
+  timeout -k 10 600 python3 bench.py --full --workload $W --no-e2e > "$OUT/bench_$W.json" 2> "$OUT/bench_$W.err"
   ok $? "bench_$W"
 done
 cd /tmp

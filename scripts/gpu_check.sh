@@ -22,11 +22,11 @@ ok $? pytest-gpu
 tail -5 "$OUT/pytest_gpu.log"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 ok $? smoke
-timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 ok $? bench
 cat "$OUT/bench.json"
 for W in c3 c5; do
-  timeout -k 10 600 python bench.py --workload $W --steps 20 --warmup 20 > "$OUT/bench_$W.json" 2>> "$OUT/bench.err"
+  timeout -k 10 600 python bench.py --full --workload $W --steps 20 --warmup 20 > "$OUT/bench_$W.json" 2>> "$OUT/bench.err"
   ok $? bench-$W
   cat "$OUT/bench_$W.json"
 done

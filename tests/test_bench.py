@@ -190,3 +190,36 @@ def test_fracs_over_one_are_listed():
     assert sorted(bench.fracs_over_one(line)) == ["c3.probe_roofline.traffic_frac", "roofline.mix.frac",
                                                  "x[0].frac"]
     assert bench.fracs_over_one({"roofline": {"frac": 1.0}}) == []
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_a_large_table(tmp_path, monkeypatch):
+    """--dump-outputs: every field of the result table as float32 / float64
+    .npy, values exact; a table above the byte budget is cut to a fixed sorted
+    row sample, the same on every call, and the dump stays under the budget."""
+    n = 1000
+    rng = np.random.default_rng(3)
+    res = np.zeros(n, nydus_gpu.RESULT_DTYPE)
+    res["digest"] = rng.integers(0, 256, (n, 32))
+    res["kind"] = rng.integers(0, 3, n)
+    res["index"] = np.arange(n)
+    res["ref"] = np.arange(n)
+    res["uncompressed_offset"] = np.arange(n, dtype=np.uint64) << np.uint64(24)  # past 2^32
+    st = np.zeros(3, nydus_gpu.LAYER_STATS_DTYPE)
+    st["chunks"] = [400, 300, 300]
+    info = bench.dump_outputs(str(tmp_path / "all"), res, st)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == sorted(info["arrays"]) and info["rows"] == info["of"] == n
+    assert got["digest"].dtype == np.float32 and (got["digest"] == res["digest"]).all()
+    for f in ("kind", "index", "ref", "blob_index", "dict_blob", "uncompressed_offset"):
+        assert got[f].dtype == np.float64 and (got[f] == res[f]).all(), f
+    assert (got["rows"] == np.arange(n)).all()
+    assert got["layer_stats"].shape == (3, len(st.dtype.names)) and (got["layer_stats"][:, 0] == st["chunks"]).all()
+    # a budget of 100 rows: a seeded sample, sorted, identical on a second call
+    per_row = 32 * 4 + 8 * 7
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * per_row)
+    a = bench.dump_outputs(str(tmp_path / "a"), res)
+    b = bench.dump_outputs(str(tmp_path / "b"), res, rank=1)
+    assert a["rows"] == 100 and a["of"] == n and a["bytes"] <= 100 * per_row
+    ra, rb = np.load(tmp_path / "a" / "rows.npy"), np.load(tmp_path / "b" / "rows_rank1.npy")
+    assert (ra == rb).all() and (np.diff(ra) > 0).all() and len(ra) == 100
+    assert (np.load(tmp_path / "a" / "digest.npy") == res["digest"][ra.astype(np.int64)]).all()

@@ -19,7 +19,7 @@ def test_bench_gpus_2_self_launches_two_ranks():
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--workload", "c1", "--steps", "3", "--no-sub", "--settle-s", "0.2"]
+           "--workload", "c1", "--steps", "3", "--full", "--no-sub", "--settle-s", "0.2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=170, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith('{"metric"')]
@@ -52,3 +52,40 @@ def test_bench_packs_over_a_node_reports_placement_and_every_chunk():
     placed = m["packs_per_node_part_last_round"]
     assert len(placed) == 2 and sum(placed) == 8 and min(placed) > 0, placed
     assert sum(m["decisions_last_round"].values()) == m["chunks_per_round"] > 0, m
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_result_table(tmp_path):
+    """A plain run (no --full) of a small layer: the line carries the headline
+    fields and the steps asked for, none of the entries that take work of
+    their own, and --dump-outputs leaves the last step's result table as
+    float arrays (8 distinct 1 MiB chunks: every one NEW, in order)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "l8m",
+           "--steps", "3", "--warmup", "2", "--settle-s", "0", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=100, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert abs(d["value"] - d["config"]["file_bytes_per_gpu"] / d["ms_per_step"] / 1e6) <= 0.02 * d["value"]
+    assert d["cpu_baseline"] is None and d["e2e_pcie"] is None
+    for k in ("c1", "c3", "c5_1000", "packs_c1", "speedup_vs_cpu", "digest_check_past_4gib"):
+        assert k not in d, k
+    n = d["config"]["chunks"]
+    assert n == 8 and d["dump_outputs"]["rows"] == n
+    got = {p.name[:-4]: np.load(p) for p in out.iterdir()}
+    assert sorted(got) == sorted(["rows", "digest", "kind", "index", "ref", "blob_index",
+                                  "dict_blob", "uncompressed_offset"])
+    assert got["digest"].dtype == np.float32 and got["digest"].shape == (n, 32)
+    assert all(a.dtype == np.float64 and a.shape == (n,) for k, a in got.items() if k != "digest")
+    dg = got["digest"]
+    assert (dg == np.floor(dg)).all() and dg.min() >= 0 and dg.max() <= 255
+    assert len({r_.tobytes() for r_ in dg}) == n  # random chunks: distinct digests
+    assert (got["kind"] == 0).all() and (got["index"] == np.arange(n)).all()
+    assert (got["rows"] == np.arange(n)).all()
+    assert (got["uncompressed_offset"] == np.arange(n) * float(1 << 20)).all()

@@ -4,23 +4,49 @@ only entry points include/nydus_gpu.h declares.  No Go toolchain here: the
 Go files are checked as text."""
 import os
 import re
-import shutil
 import subprocess
-
-import pytest
 
 from conftest import ROOT
 
-REF = "/root/reference"
 GO = os.path.join(ROOT, "integration", "go")
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "pkg", "converter")),
-                    reason="reference tree not present (GPU box)")
+def patch_preimages(text):
+    """{path: old file} for a unified diff, from the patch alone: every hunk's
+    context and removed lines at the old-file line numbers its header states,
+    numbered filler lines between the hunks.  A hunk whose header disagrees
+    with its body, or that overlaps the one before, fails here."""
+    files, path, lines, want = {}, None, None, 0
+    for ln in text.splitlines():
+        if want == 0 and ln.startswith("--- a/"):
+            path = ln[6:].split("\t")[0]
+            lines = files.setdefault(path, [])
+        elif want == 0 and ln.startswith("@@ "):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+\d+(?:,\d+)? @@", ln)
+            start, want = int(m.group(1)), int(m.group(2) or 1)
+            assert path and start > len(lines), (path, ln)
+            lines += [f"// line {i}" for i in range(len(lines) + 1, start)]
+        elif want and ln[:1] in (" ", "-"):
+            lines.append(ln[1:])
+            want -= 1
+        else:
+            assert ln[:1] == "+" or want == 0, (path, ln)
+    assert want == 0
+    return {p: "\n".join(l) + "\n" for p, l in files.items()}
+
+
 def test_converter_patch_applies_to_the_reference(tmp_path):
-    for f in ("pkg/converter/types.go", "pkg/converter/convert_unix.go", "pkg/converter/tool/builder.go"):
+    """The patch applies, hunk by hunk, to the converter sources it was cut
+    from.  Those are the reference's and are not kept here, so the old files
+    are rebuilt from the patch's own hunks (patch_preimages): `git apply`
+    then checks every hunk's counts and position, and the patched files hold
+    the GPU branches."""
+    pre = patch_preimages(open(os.path.join(GO, "converter.patch")).read())
+    assert sorted(pre) == ["pkg/converter/convert_unix.go", "pkg/converter/tool/builder.go",
+                           "pkg/converter/types.go"]
+    for f, text in pre.items():
         os.makedirs(tmp_path / os.path.dirname(f), exist_ok=True)
-        shutil.copy(os.path.join(REF, f), tmp_path / f)
+        (tmp_path / f).write_text(text)
     subprocess.check_call(["git", "init", "-q", str(tmp_path)])
     subprocess.check_call(["git", "-C", str(tmp_path), "apply", "-p1",
                            os.path.join(GO, "converter.patch")])
