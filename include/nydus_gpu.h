@@ -465,7 +465,9 @@ typedef struct {
   uint64_t pack_pool;           /* per-pack stream + buffer sets kept */
   uint64_t land_pool;           /* early-emission landing buffers kept */
   uint64_t batch_waitable;      /* open packs a batch leader would still wait for */
-  uint64_t reserved[2];
+  uint64_t check_windows;       /* staging windows Check has sent to the GPU so far (a
+                                   reserved word until Check; still ABI 7) */
+  uint64_t reserved[1];
 } ngpu_engine_counters;
 int ngpu_engine_counters_get(ngpu_engine *eng, ngpu_engine_counters *out);
 
@@ -738,6 +740,107 @@ int ngpu_unpack_entry(ngpu_read_at_fn ra, void *ctx, uint64_t size, const char *
  * another blob (a chunk-dict blob) is NGPU_ENOTFOUND: only the layer's own
  * blob travels in its stream. */
 int ngpu_unpack(ngpu_read_at_fn ra, void *ctx, uint64_t size, ngpu_write_fn w, void *wctx);
+
+/* ---- Check: re-digest a converted layer's chunks (additive in ABI 7) --------
+ * The reference proves a conversion by reading it back: `nydusify check`
+ * closes TestImageConvert (tests/converter_test.go:865-875) and nydusd
+ * validates chunk digests when it serves them (`digest_validate`,
+ * tests/nydusd.go:69).  Here: every chunk record of a bootstrap is read from
+ * its blob, inflated on the host, hashed again on the GPU and compared with the
+ * record's block_id.
+ *
+ * ngpu_check_device: the device stage, device pointers, async on `stream`
+ * (no host wait).  The digest stage of ngpu_digest_device into d_out, then
+ * the verdict kernel: bit i % 64 of d_bitmap[i / 64] is set iff d_out[i].kind
+ * != NGPU_DIGESTED or the 32 digest bytes differ from d_expected + i *
+ * expected_stride.  d_counts[0] = set bits, d_counts[1] = how many of them
+ * were not NGPU_DIGESTED.  The call writes every one of the (n + 63) / 64
+ * bitmap words (zero words and the zero tail bits of the last one included)
+ * and zeroes d_counts itself on `stream`: the caller clears nothing.
+ * expected_stride >= 32 and a multiple of 4, d_expected 4-byte aligned
+ * (NGPU_EINVAL otherwise); 16-byte loads when d_expected and the stride are
+ * 16-byte aligned -- 32, or 80 to read the block_id of RAFS v6 chunk-info
+ * records in place -- dword loads otherwise.  n == 0 only zeroes the counts;
+ * n >= 0xFFFFFFFF is NGPU_EINVAL.  Locking and workspace use as
+ * ngpu_digest_device. */
+int ngpu_check_device(ngpu_engine *eng, const void *d_data, uint64_t len,
+                      const ngpu_chunk *d_chunks, uint64_t n, ngpu_result *d_out,
+                      const uint8_t *d_expected, uint64_t expected_stride,
+                      uint64_t *d_bitmap /* (n + 63) / 64 words */,
+                      uint64_t *d_counts /* 2 words */, void *stream);
+
+/* A blob offered to ngpu_check_image: `id` is the blob id in the bootstrap's
+ * blob table (64 hex chars); the reader is the blob's chunk data (image.blob)
+ * or a whole layer stream -- a record's compressed_offset counts from offset
+ * 0 in both.  ra may be called from several threads at once (content.ReaderAt
+ * allows it). */
+typedef struct {
+  const char *id;
+  ngpu_read_at_fn ra;
+  void *ctx;
+  uint64_t size;
+} ngpu_check_blob;
+typedef struct {
+  uint32_t flags;        /* reserved, 0 */
+  uint32_t threads;      /* host inflate threads; 0 -> min(16, cores) */
+  uint64_t window_bytes; /* staging window; 0 -> the engine's staging_bytes */
+} ngpu_check_options;
+typedef struct {
+  uint64_t records;      /* distinct chunk records of the bootstrap */
+  uint64_t checked;      /* read from a supplied blob and compared (bad ones included) */
+  uint64_t bad;          /* failures of any reason, listed or not */
+  uint64_t dict_checked; /* records of blobs not supplied, resolved in the dict */
+  uint64_t dict_bad;     /* of which NGPU_CHECK_DICT failures (counted in bad too) */
+  uint64_t skipped;      /* records of blobs not supplied, no dict given */
+  uint64_t bytes;        /* uncompressed bytes hashed on the GPU */
+} ngpu_check_report;
+enum {
+  NGPU_CHECK_DIGEST = 1,     /* the chunk's bytes do not hash to its block_id */
+  NGPU_CHECK_DECOMPRESS = 2, /* the chunk does not inflate to its uncompressed size */
+  NGPU_CHECK_RANGE = 3,      /* compressed range outside the blob, or an uncompressed
+                                size of 0 or above the chunk size */
+  NGPU_CHECK_DICT = 4        /* not resolved by the chunk dict */
+};
+typedef struct {
+  uint32_t blob_index, index, reason, uncompressed_size; /* the record's fields + why */
+  uint64_t compressed_offset;
+  uint8_t expected[32]; /* the record's block_id */
+  uint8_t got[32];      /* NGPU_CHECK_DIGEST: the digest of the bytes read; else zeros */
+} ngpu_check_bad;
+
+/* Check every distinct chunk record of a RAFS v6 bootstrap (its chunk table,
+ * table order) or v5 bootstrap (distinct (blob, index) over the regular files'
+ * chunks, inode-table order) once.  A record whose blob is among `blobs`
+ * (matched by id) is bounds-checked against the blob's size, inflated with the
+ * blob's compressor on `threads` host threads (copied when stored raw) into a
+ * pinned window, copied to HBM and run through ngpu_check_device beside its
+ * expected digest; only the bitmap and counts come back, and the results of
+ * windows that hold a bad record.  The host fills one window while the GPU
+ * works on the other.  A record whose blob is not supplied is looked up in
+ * `dict` on the GPU (an engine or node dict; NULL: counted as skipped): it is
+ * NGPU_CHECK_DICT-bad unless the dict holds its digest with a matching size
+ * (dict usize 0 or equal) at the same chunk index and uncompressed offset in
+ * a blob of the same id.
+ * report->bad counts every failure; bad[0 .. min(bad, bad_cap)) lists the
+ * first ones in record order.  A failing record never stops the check.
+ * Returns 0 when the check ran to its end (read the report); NGPU_EINVAL: the
+ * bootstrap's digester or chunk size is not the engine's, or window_bytes is
+ * below the chunk size; NGPU_EUNSUPP: a targz-ref (OCIRef) bootstrap;
+ * NGPU_EFORMAT: a malformed bootstrap; NGPU_EIO: a reader failed inside a
+ * range it claimed to hold; NGPU_EDEVICE: the digest stage left records
+ * unhashed.  Untrusted input: every size is bounded before it sizes a buffer. */
+int ngpu_check_image(ngpu_engine *eng, const void *bootstrap, uint64_t size,
+                     const ngpu_check_blob *blobs, uint32_t n_blobs, ngpu_dict *dict,
+                     const ngpu_check_options *opt, ngpu_check_report *report,
+                     ngpu_check_bad *bad, uint64_t bad_cap);
+/* The same for one packed layer's nydus stream: image.boot is found as
+ * ngpu_unpack finds it, and the stream's image.blob is offered as the layer's
+ * own blob (ngpu_unpack's rule: the blob named by image.blob's TOC digest,
+ * else the one of its size).  Like ngpu_unpack it trusts the TOC for
+ * locations and does not verify the TOC's entry digests. */
+int ngpu_check_stream(ngpu_engine *eng, ngpu_read_at_fn ra, void *ctx, uint64_t size,
+                      ngpu_dict *dict, const ngpu_check_options *opt, ngpu_check_report *report,
+                      ngpu_check_bad *bad, uint64_t bad_cap);
 
 /* converter.Merge (convert_unix.go:560-666) -> tool.Merge (builder.go:220-294,
  * `nydus-image merge --prefetch-policy fs [--chunk-dict] [--parent-bootstrap]`):

@@ -1479,6 +1479,36 @@ int locate(const Reader &r, const char *name, uint64_t *off, uint64_t *len, bool
 }
 }  // namespace
 
+extern "C++" {
+namespace ngpu {
+int locate_layer(ngpu_read_at_fn ra, void *ctx, uint64_t size, LayerParts *out) {
+  Reader r{ra, ctx, size};
+  uint64_t boff, blen;
+  bool bdig;
+  uint8_t bd[32];
+  int rc = locate(r, "image.boot", &boff, &blen, &bdig, bd);
+  if (rc) return rc;
+  if (blen > (8ull << 30)) return host_fail(NGPU_EFORMAT, "bootstrap of %llu bytes", (unsigned long long)blen);
+  out->boot.resize(blen);
+  if ((rc = r.read(out->boot.data(), blen, boff))) return rc;
+  rc = locate(r, "image.blob", &out->data_off, &out->data_len, &out->have_digest, out->data_digest);
+  out->has_data = rc == 0;
+  if (rc == NGPU_ENOTFOUND) rc = 0;  // a layer with no chunk of its own
+  return rc;
+}
+
+int own_blob_of(const std::vector<RafsV6BlobInfo> &blobs, const LayerParts &lp) {
+  if (!lp.has_data) return -1;
+  const std::string want = lp.have_digest ? hex(lp.data_digest, 32) : std::string();
+  for (size_t i = 0; i < blobs.size(); ++i)
+    if (!want.empty() && blob_id_of(blobs[i]) == want) return (int)i;
+  for (size_t i = 0; i < blobs.size() && lp.data_len && want.empty(); ++i)
+    if (blobs[i].compressed_size == lp.data_len) return (int)i;
+  return -1;
+}
+}  // namespace ngpu
+}  // extern "C++"
+
 int ngpu_unpack(ngpu_read_at_fn ra, void *ctx, uint64_t size, ngpu_write_fn w, void *wctx) {
   const int rc = guarded([&]() -> int {
     if (!ra || !w) return host_fail(NGPU_EINVAL, "ngpu_unpack: bad argument");

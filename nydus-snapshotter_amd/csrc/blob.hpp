@@ -147,6 +147,21 @@ const Codecs &codecs();
 int decompress_chunk(uint32_t algo, const uint8_t *src, uint64_t csize, uint8_t *dst,
                      uint64_t usize);
 
+// Where a packed layer's nydus stream keeps its bootstrap and its chunk data,
+// found as ngpu_unpack finds them (TOC, else tar headers from the tail): the
+// image.boot bytes, image.blob's range in the stream and, from the TOC, its
+// sha256 (the own blob's id).  has_data false: no image.blob entry.
+struct LayerParts {
+  std::vector<uint8_t> boot;
+  uint64_t data_off = 0, data_len = 0;
+  bool has_data = false, have_digest = false;
+  uint8_t data_digest[32] = {};
+};
+int locate_layer(ngpu_read_at_fn ra, void *ctx, uint64_t size, LayerParts *out);
+// The layer's own blob among the bootstrap's blobs (ngpu_unpack's rule: the one
+// named by image.blob's digest, else the one of image.blob's size), or -1.
+int own_blob_of(const std::vector<RafsV6BlobInfo> &blobs, const LayerParts &lp);
+
 // Parsed (minimal) RAFS v6 bootstrap: blob table + chunk table.
 struct Bootstrap {
   uint64_t flags = 0;

@@ -950,6 +950,7 @@ int ngpu_engine_counters_get(ngpu_engine *e, ngpu_engine_counters *out) {
   memset(out, 0, sizeof *out);
   out->open_packs = (uint64_t)e->open_packs.load();
   out->batch_waitable = (uint64_t)e->batch_waitable.load();
+  out->check_windows = e->check_windows.load();
   std::lock_guard<std::mutex> g(e->pool_mu);
   out->staging_pool_bufs = e->staging_pool.size();
   out->staging_pool_bytes = e->staging_pool_bytes;

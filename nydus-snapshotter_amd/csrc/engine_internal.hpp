@@ -164,6 +164,7 @@ struct ngpu_engine {
   // open packs that may still join a batch at close (one staging slot of tar
   // so far, not OCIRef, batching on): what a batch leader waits for
   std::atomic<int> batch_waitable{0};
+  std::atomic<uint64_t> check_windows{0};  // windows ngpu_check_* enqueued (engine counters)
   uint64_t uid = 0;          // unique for the process's lifetime (node exchange channels)
   ngpu_config cfg{};
   int device = 0;
@@ -277,6 +278,25 @@ bool ws_lazy_end(const ngpu_engine *e, hipStream_t s, bool chained);
 // bound: the stage-end event its last kernel records (null: record ws_done,
 // or nothing when ws_lazy_end).
 int ws_release(ngpu_engine *e, hipStream_t s, hipEvent_t bound, bool chained);
+
+// The engine's pool of staging slots (pack.hip), shared by the streaming Packs
+// and Check.  A slot is `cap` pinned bytes (h), optionally as many in HBM (d),
+// pinned + device chunk lists of staging_slot_chunks(cap) descriptors and two
+// events; only slots of the engine's own capacity (staging_slot_cap) are pooled.
+uint64_t staging_slot_cap(const ngpu_engine *e);
+inline uint64_t staging_slot_chunks(uint64_t cap) {
+  return cap / 1024 + 16;  // a chunk costs >= 1 KiB of tar stream unless it is a file's last
+}
+// A pooled slot of at least `bytes` into *b (b->h null: none).
+void staging_pool_take(ngpu_engine *e, uint64_t bytes, ngpu_staging_buf *b);
+// Pinned + device buffers of at least `bytes`: a pooled slot (its HBM half
+// allocated if it came without), else a new one -- a whole poolable slot when
+// `bytes` is more than half a slot, just the bytes otherwise.  false: out of
+// memory (staging_give what *b holds).
+bool staging_take(ngpu_engine *e, uint64_t bytes, ngpu_staging_buf *b);
+// Back to the pool when it is a whole slot and the pool has room, freed
+// otherwise; nothing may still use it.  *b is cleared.
+void staging_give(ngpu_engine *e, ngpu_staging_buf &b);
 
 // Reference counts.  engine_unref frees the engine when the last holder (the
 // creator's ngpu_destroy or the last open pack) lets go.

@@ -282,25 +282,10 @@ void release(ngpu_pack *p) {
   }
   if (p->stream) (void)hipStreamSynchronize(p->stream);
   ptrace(p, "release_synced");
-  {
-    std::lock_guard<std::mutex> g(p->e->pool_mu);
-    for (Slot &s : p->slot) {
-      if (!s.h || !s.h_ch || !s.d_ch || !s.copied || !s.done ||
-          p->e->staging_pool.size() >= ngpu_engine::kStagingPool ||
-          p->e->staging_pool_bytes + p->cap > ngpu_engine::kStagingPoolBytes)
-        continue;
-      p->e->staging_pool.push_back({s.h, s.h_ch, s.d, s.d_ch, s.copied, s.done, p->cap});
-      p->e->staging_pool_bytes += p->cap;
-      s = Slot{};
-    }
-  }
-  for (Slot &s : p->slot) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.h_ch) (void)hipHostFree(s.h_ch);
-    if (s.d) (void)hipFree(s.d);
-    if (s.d_ch) (void)hipFree(s.d_ch);
-    if (s.copied) (void)hipEventDestroy(s.copied);
-    if (s.done) (void)hipEventDestroy(s.done);
+  for (Slot &s : p->slot) {  // whole slots go back to the engine's pool
+    ngpu_staging_buf b{s.h, s.h_ch, s.d, s.d_ch, s.copied, s.done, p->cap};
+    staging_give(p->e, b);
+    s = Slot{};
   }
   for (ngpu_pack::Arena &ar : p->arenas) (void)hipFreeAsync(ar.d, p->stream);  // the streams are idle
   ptrace(p, "release_segments");
@@ -947,6 +932,66 @@ void emit_stop(ngpu_pack *p) {
 
 }  // namespace
 
+namespace ngpu {
+
+uint64_t staging_slot_cap(const ngpu_engine *e) {
+  return std::max<uint64_t>(e->cfg.staging_bytes, 4ull * e->cfg.chunk_size);
+}
+
+void staging_pool_take(ngpu_engine *e, uint64_t bytes, ngpu_staging_buf *b) {
+  *b = ngpu_staging_buf{};
+  std::lock_guard<std::mutex> g(e->pool_mu);
+  auto &pool = e->staging_pool;
+  for (size_t i = 0; i < pool.size(); ++i) {
+    if (pool[i].cap < bytes) continue;
+    *b = pool[i];
+    pool.erase(pool.begin() + (long)i);
+    e->staging_pool_bytes -= b->cap;
+    return;
+  }
+}
+
+bool staging_take(ngpu_engine *e, uint64_t bytes, ngpu_staging_buf *b) {
+  staging_pool_take(e, bytes, b);
+  if (b->h) return b->d || hipMalloc(&b->d, b->cap) == hipSuccess;
+  const uint64_t slot = staging_slot_cap(e);
+  const bool whole = bytes <= slot && bytes * 2 > slot;
+  b->cap = whole ? slot : std::max<uint64_t>(bytes, 64);
+  bool ok = hipHostMalloc(&b->h, b->cap, hipHostMallocDefault) == hipSuccess &&
+            hipMalloc(&b->d, b->cap) == hipSuccess;
+  if (ok && whole) {
+    const uint64_t max_ch = staging_slot_chunks(b->cap);
+    ok = hipHostMalloc(&b->h_ch, max_ch * sizeof(ngpu_chunk), hipHostMallocDefault) == hipSuccess &&
+         hipMalloc(&b->d_ch, max_ch * sizeof(ngpu_chunk)) == hipSuccess &&
+         hipEventCreateWithFlags(&b->copied, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&b->done, hipEventDisableTiming) == hipSuccess;
+  }
+  if (!ok) (void)hipGetLastError();
+  return ok;
+}
+
+void staging_give(ngpu_engine *e, ngpu_staging_buf &b) {
+  if (b.h && b.h_ch && b.d_ch && b.copied && b.done && b.cap == staging_slot_cap(e)) {
+    std::lock_guard<std::mutex> g(e->pool_mu);
+    if (e->staging_pool.size() < ngpu_engine::kStagingPool &&
+        e->staging_pool_bytes + b.cap <= ngpu_engine::kStagingPoolBytes) {
+      e->staging_pool.push_back(b);
+      e->staging_pool_bytes += b.cap;
+      b = ngpu_staging_buf{};
+      return;
+    }
+  }
+  if (b.h) (void)hipHostFree(b.h);
+  if (b.h_ch) (void)hipHostFree(b.h_ch);
+  if (b.d) (void)hipFree(b.d);
+  if (b.d_ch) (void)hipFree(b.d_ch);
+  if (b.copied) (void)hipEventDestroy(b.copied);
+  if (b.done) (void)hipEventDestroy(b.done);
+  b = ngpu_staging_buf{};
+}
+
+}  // namespace ngpu
+
 void blob_windows_free(BlobWindows &w) {
   for (int i = 0; i < 2; ++i) {
     if (w.dwin[i]) (void)hipFree(w.dwin[i]);
@@ -993,10 +1038,9 @@ static int pack_open(ngpu_engine *e, ngpu_dict *dict, uint32_t flags, ngpu_pack 
   }
   // the stream's bootstrap lists every entry (OCIRef: the bootstrap is all it carries)
   if (p->retain || p->gz) p->sc.record(&p->entries);
-  uint64_t cap = e->cfg.staging_bytes;
-  if (cap < 4ull * e->cfg.chunk_size) cap = 4ull * e->cfg.chunk_size;
+  const uint64_t cap = staging_slot_cap(e);
   p->cap = cap;
-  p->max_ch = cap / 1024 + 16;  // a chunk costs >= 1 KiB of tar stream unless it is a file's last
+  p->max_ch = staging_slot_chunks(cap);
   bool ok = true;
   {
     std::lock_guard<std::mutex> pg(e->pool_mu);
@@ -1014,22 +1058,17 @@ static int pack_open(ngpu_engine *e, ngpu_dict *dict, uint32_t flags, ngpu_pack 
       p->all_cap = b.all_cap;
       p->win = b.win;
     }
-    for (Slot &s : p->slot) {
-      auto &pool = e->staging_pool;
-      for (size_t i = 0; i < pool.size(); ++i) {
-        if (pool[i].cap != cap) continue;
-        const ngpu_staging_buf b = pool[i];
-        pool.erase(pool.begin() + (long)i);
-        e->staging_pool_bytes -= b.cap;
-        s.h = (uint8_t *)b.h;
-        s.h_ch = (ngpu_chunk *)b.h_ch;
-        s.d = (uint8_t *)b.d;
-        s.d_ch = (ngpu_chunk *)b.d_ch;
-        s.copied = b.copied;
-        s.done = b.done;
-        break;
-      }
-    }
+  }
+  for (Slot &s : p->slot) {
+    ngpu_staging_buf b;
+    staging_pool_take(e, cap, &b);  // (pooled slots all have the engine's capacity)
+    if (!b.h) break;
+    s.h = (uint8_t *)b.h;
+    s.h_ch = (ngpu_chunk *)b.h_ch;
+    s.d = (uint8_t *)b.d;
+    s.d_ch = (ngpu_chunk *)b.d_ch;
+    s.copied = b.copied;
+    s.done = b.done;
   }
   {  // the pack's shared copy lanes (created with the engine's first pack)
     const uint32_t k = e->copy_rr++ % ngpu_engine::kCopyLanes;

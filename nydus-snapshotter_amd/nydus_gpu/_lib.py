@@ -74,7 +74,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # ABI 5
            "ngpu_node_process_step", "ngpu_batch_stats",
            # ABI 7
-           "ngpu_pack_engine", "ngpu_engine_counters_get", "ngpu_merge_ex2"]
+           "ngpu_pack_engine", "ngpu_engine_counters_get", "ngpu_merge_ex2",
+           # Check (additive in ABI 7)
+           "ngpu_check_device", "ngpu_check_image", "ngpu_check_stream"]
 
 LAYER_STATS_DTYPE = np.dtype([("chunks", "<u8"), ("new_chunks", "<u8"), ("intra_chunks", "<u8"),
                               ("dict_chunks", "<u8"), ("new_bytes", "<u8"), ("own_blob_index", "<u4"),
@@ -141,6 +143,30 @@ class NgpuBlobInfo(ctypes.Structure):
         for k in ("stream_digest", "blob_digest", "toc_digest"):
             d[k] = bytes(getattr(self, k)).hex()
         return d
+
+
+class NgpuCheckBlob(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_char_p), ("ra", READ_AT_FN), ("ctx", ctypes.c_void_p),
+                ("size", ctypes.c_uint64)]
+
+
+class NgpuCheckOptions(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32), ("threads", ctypes.c_uint32),
+                ("window_bytes", ctypes.c_uint64)]
+
+
+class NgpuCheckReport(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("records", "checked", "bad", "dict_checked",
+                                               "dict_bad", "skipped", "bytes")]
+
+
+# ngpu_check_bad.reason
+CHECK_DIGEST, CHECK_DECOMPRESS, CHECK_RANGE, CHECK_DICT = 1, 2, 3, 4
+CHECK_REASONS = {1: "DIGEST", 2: "DECOMPRESS", 3: "RANGE", 4: "DICT"}
+CHECK_BAD_DTYPE = np.dtype([("blob_index", "<u4"), ("index", "<u4"), ("reason", "<u4"),
+                            ("uncompressed_size", "<u4"), ("compressed_offset", "<u8"),
+                            ("expected", "u1", (32,)), ("got", "u1", (32,))])
+assert CHECK_BAD_DTYPE.itemsize == 88
 
 
 class NgpuError(RuntimeError):
@@ -258,6 +284,12 @@ def lib():
     L.ngpu_node_pack_open.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
     L.ngpu_node_process_device.argtypes = [vp, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp]
     L.ngpu_node_process_step.argtypes = [vp, vp, ctypes.POINTER(NgpuNodePart), u32, u32]
+    L.ngpu_check_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
+    L.ngpu_check_image.argtypes = [vp, vp, u64, ctypes.POINTER(NgpuCheckBlob), u32, vp,
+                                   ctypes.POINTER(NgpuCheckOptions), ctypes.POINTER(NgpuCheckReport),
+                                   vp, u64]
+    L.ngpu_check_stream.argtypes = [vp, READ_AT_FN, vp, u64, vp, ctypes.POINTER(NgpuCheckOptions),
+                                    ctypes.POINTER(NgpuCheckReport), vp, u64]
     _lib = L
     return L
 
@@ -438,6 +470,19 @@ def unpack(blob, dest=None):
     sink.reraise()
     _host_check(rc, "unpack")
     return None if dest is not None else b"".join(out)
+
+
+def _mem_reader(src):
+    """A READ_AT_FN over a uint8 numpy buffer (keep the returned object alive
+    for the call).  ctypes.memmove runs without the GIL, so the library's
+    reader threads copy side by side."""
+    def ra(_ctx, buf, n, off):
+        n = min(n, src.size - off)
+        if n <= 0:
+            return -1
+        ctypes.memmove(buf, src.ctypes.data + off, n)
+        return n
+    return READ_AT_FN(ra)
 
 
 def rafs_dump(bootstrap: bytes) -> dict:
@@ -725,6 +770,63 @@ class Engine:
         self._check(lib().ngpu_digest_device(self._h, self._vp(d_data), length, self._vp(d_chunks),
                                              n, self._vp(d_out), self._vp(stream)), "digest_device")
 
+    def check_device(self, d_data: int, length: int, d_chunks: int, n: int, d_out: int,
+                     d_expected: int, expected_stride: int, d_bitmap: int, d_counts: int,
+                     stream: int = 0):
+        """ngpu_check_device: the digest stage into d_out, then the verdict kernel
+        (bit i set: record i is not DIGESTED or differs from d_expected + i *
+        stride; d_counts = [set bits, of which not DIGESTED]).  Async on `stream`."""
+        self._check(lib().ngpu_check_device(
+            self._h, self._vp(d_data), length, self._vp(d_chunks), n, self._vp(d_out),
+            self._vp(d_expected), expected_stride, self._vp(d_bitmap), self._vp(d_counts),
+            self._vp(stream)), "check_device")
+
+    @staticmethod
+    def _check_report(rep, bad):
+        d = {k: getattr(rep, k) for k, _ in rep._fields_}
+        d["bad_list"] = [{"blob_index": int(b["blob_index"]), "index": int(b["index"]),
+                          "reason": CHECK_REASONS.get(int(b["reason"]), int(b["reason"])),
+                          "uncompressed_size": int(b["uncompressed_size"]),
+                          "compressed_offset": int(b["compressed_offset"]),
+                          "expected": b["expected"].tobytes().hex(), "got": b["got"].tobytes().hex()}
+                         for b in bad[:min(rep.bad, len(bad))]]
+        return d
+
+    def check(self, stream, dict=None, max_bad: int = 64, window_bytes: int = 0, threads: int = 0):
+        """ngpu_check_stream: re-digest every chunk of a packed layer's nydus
+        stream (bytes / numpy buffer) on the GPU against its image.boot.  Returns
+        the report as a dict with a "bad_list" of at most max_bad failures in
+        record order.  dict: a ChunkDict that must resolve the records of blobs
+        the stream does not carry (None: they are counted as skipped)."""
+        src = _buf(stream)
+        rfn = _mem_reader(src)
+        opt = NgpuCheckOptions(0, threads, window_bytes)
+        rep = NgpuCheckReport()
+        bad = np.zeros(max_bad, CHECK_BAD_DTYPE)
+        self._check(lib().ngpu_check_stream(self._h, rfn, None, src.size, _dict_arg(dict),
+                                            ctypes.byref(opt), ctypes.byref(rep), _ptr(bad), max_bad),
+                    "check")
+        return self._check_report(rep, bad)
+
+    def check_image(self, boot, blobs, dict=None, max_bad: int = 64, window_bytes: int = 0,
+                    threads: int = 0):
+        """ngpu_check_image: every distinct chunk record of a RAFS v5 / v6
+        bootstrap against the blobs given as {blob id (hex): bytes} -- image.blob
+        data or whole layer streams; records of other blobs go to `dict`."""
+        b = _buf(boot)
+        srcs = [(k.encode(), _buf(v)) for k, v in blobs.items()]
+        fns = [_mem_reader(v) for _, v in srcs]
+        arr = (NgpuCheckBlob * max(1, len(srcs)))()
+        for i, ((k, v), fn) in enumerate(zip(srcs, fns)):
+            arr[i] = NgpuCheckBlob(k, fn, None, v.size)
+        opt = NgpuCheckOptions(0, threads, window_bytes)
+        rep = NgpuCheckReport()
+        bad = np.zeros(max_bad, CHECK_BAD_DTYPE)
+        self._check(lib().ngpu_check_image(self._h, _ptr(b), b.size, arr, len(srcs), _dict_arg(dict),
+                                           ctypes.byref(opt), ctypes.byref(rep), _ptr(bad), max_bad),
+                    "check_image")
+        return self._check_report(rep, bad)
+
     def dict_probe_device(self, d_digests: int, stride: int, n: int, d_hits: int, stream: int = 0):
         self._check(lib().ngpu_dict_probe_device(self._h, self._vp(d_digests), stride, n,
                                                  self._vp(d_hits), self._vp(stream)), "dict_probe_device")
@@ -776,7 +878,7 @@ class Engine:
         out = (ctypes.c_uint64 * 8)()
         self._check(lib().ngpu_engine_counters_get(self._h, out), "engine_counters")
         keys = ("open_packs", "staging_pool_bufs", "staging_pool_bytes", "pack_pool", "land_pool",
-                "batch_waitable")
+                "batch_waitable", "check_windows")
         return {k: int(out[i]) for i, k in enumerate(keys)}
 
     def timing_at(self, back: int) -> dict:
@@ -1038,6 +1140,13 @@ class Node:
         w._cancel = ctypes.c_int32(0)
         lib().ngpu_pack_set_cancel(w._p, ctypes.byref(w._cancel))
         return w
+
+    def check(self, stream, dict=None, max_bad: int = 64, window_bytes: int = 0, threads: int = 0):
+        """Engine.check on the node's least-loaded engine (fewest open packs);
+        dict: a node dict (partitioned or replicated) or None."""
+        c = [e.counters()["open_packs"] for e in self.engines]
+        return self.engines[c.index(min(c))].check(stream, dict=dict, max_bad=max_bad,
+                                                   window_bytes=window_bytes, threads=threads)
 
     def process_step(self, dict, parts, rccl: bool = False):
         """ngpu_node_process_step: every device's part at once, one all-to-all-v

@@ -18,7 +18,16 @@ usage:
   python -m nydus_gpu.inspect --tree FILE     # JSON dump of the inode tree
   python -m nydus_gpu.inspect --diff A B      # exit 0 iff the chunk sets match
   python -m nydus_gpu.inspect --diff --tree A B  # exit 0 iff the trees match
+  python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP] [--chunk-size N] [--digester D]
+                                              # re-digest STREAM's chunks on the GPU; exit 1 if any is bad
 FILE may be a bootstrap (image.boot) or a whole Pack output stream.
+
+`--check` (Engine.check, ngpu_check_stream) needs a GPU: every chunk record of
+the stream's image.boot is read from its image.blob, inflated, hashed on the GPU
+and compared with the record's digest; records of other blobs must resolve in
+the `--dict` chunk-dict bootstrap (without one they are counted as skipped).
+The digester, chunk size and RAFS version default to the stream's own; the
+report is printed as JSON.
 """
 from __future__ import annotations
 
@@ -112,12 +121,54 @@ def diff(a: dict, b: dict, fields=("digest", "blob_id", "uncompressed_size")) ->
     return [("-", k) for k in sorted(ka - kb)] + [("+", k) for k in sorted(kb - ka)]
 
 
+def check(path: str, dict_path: str = None, chunk_size: int = 0, digester: str = None,
+          max_bad: int = 64) -> dict:
+    """Engine.check of the stream in `path` on GPU 0 (the report dict)."""
+    from ._lib import Engine
+    data = np.fromfile(path, np.uint8)
+    boot = bootstrap_bytes(data)
+    v6 = rafs.detect_fs_version(boot) == "v6"
+    if v6:
+        b = rafs.read_v6(boot)
+        flags, cs = int(b["flags"]), int(b["chunk_size"])
+    else:
+        d = rafs_dump(boot)
+        flags, cs = int(d["flags"]), int(d["chunk_size"])
+    with Engine(device=0, digester=digester or ("sha256" if flags & 0x8 else "blake3"),
+                chunk_size=chunk_size or cs, fs_version=6 if v6 else 5) as eng:
+        dct = eng.dict_open(dict_path) if dict_path else None
+        try:
+            return eng.check(data, dict=dct, max_bad=max_bad)
+        finally:
+            if dct is not None:
+                dct.release()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nydus_gpu.inspect")
-    ap.add_argument("files", nargs="+")
+    ap.add_argument("files", nargs="*")
+    ap.add_argument("--check", metavar="STREAM", help="re-digest a Pack output stream's chunks on the GPU")
+    ap.add_argument("--dict", metavar="BOOTSTRAP", help="--check: chunk-dict bootstrap for DICT records")
+    ap.add_argument("--chunk-size", type=lambda x: int(x, 0), default=0, help="--check: engine chunk size")
+    ap.add_argument("--digester", choices=("blake3", "sha256"), help="--check: engine digester")
     ap.add_argument("--diff", action="store_true", help="compare the chunk sets of two files")
     ap.add_argument("--tree", action="store_true", help="the inode tree instead of the chunk set")
     args = ap.parse_args(argv)
+    if args.check:
+        try:
+            import torch  # noqa: F401  (one HIP runtime per process: before the library)
+        except ImportError:
+            pass
+        try:
+            rep = check(args.check, args.dict, args.chunk_size, args.digester)
+        except (NgpuError, ValueError) as e:
+            print(f"check: {e}", file=sys.stderr)
+            return 2
+        json.dump(rep, sys.stdout, indent=1)
+        print()
+        return 1 if rep["bad"] else 0
+    if not args.files:
+        ap.error("no file given")
     if args.tree:
         dumps = [tree(open(f, "rb").read()) for f in args.files]
     else:
