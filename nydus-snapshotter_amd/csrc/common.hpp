@@ -66,7 +66,10 @@ __device__ __forceinline__ uint32_t rotr32(uint32_t x, uint32_t n) {
 
 // 64-bit hash-table slot: tag (digest word 2) in the high half, id in the low.
 // Equal digests give equal tags, so an atomic min over a slot keeps the
-// smallest id ("first in stream / table order wins").
+// smallest id ("first in stream / table order wins").  Word 2 == 0xFFFFFFFF
+// is stored as 0xFFFFFFFE so that no slot equals kEmpty: two digests that
+// differ only in that word then share a tag and are told apart by the full
+// compare (the tagff case of tests/dedup_cases.py).
 __device__ __forceinline__ uint32_t digest_tag(const uint32_t *w) {
   uint32_t t = w[2];
   return t == 0xFFFFFFFFu ? 0xFFFFFFFEu : t;

@@ -13,8 +13,11 @@
 // Sequential "first occurrence" becomes an atomic MIN over chunk ids in an
 // HBM hash table; sequential index assignment becomes an exclusive scan;
 // blob-index allocation in first-hit order becomes a rank over first-hit
-// positions.  Results are bit-identical to the sequential restatement
-// (oracle/dedup_ref.c) for any schedule.
+// positions.  Every path below (launch_dedup picks one by call shape) must
+// give the sequential restatement's results (oracle/dedup_ref.c) bit for bit;
+// tests/test_gpu_dedup_collisions.py holds each of them to that on crafted
+// digests: equal tags on unequal digests, equal digests at other lengths, the
+// tag remap, wrapping probe chains, one hot slot, offsets past 2^32.
 //
 // Hash table: open addressing, linear probing over 8-byte slots
 // {tag = digest word 2 : id}; bucket = (digest words 0,1) * golden ratio.

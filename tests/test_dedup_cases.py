@@ -1,0 +1,313 @@
+"""The crafted-digest dedup cases (dedup_cases.py) on the CPU: the builder
+makes what it says, the oracle agrees with a second, independent statement of
+the dedup rules on every case, and the call shapes of the GPU matrix
+(test_gpu_dedup_collisions.py) select the kernels their labels name.
+
+oracle/dedup_ref.c keeps its own open-addressing table keyed on digest bytes
+8-15 -- exactly the bytes a tagchain group shares -- so the expectation the GPU
+is held to must not rest on it alone: model_dedup() below restates the three
+rules at the top of dedup_ref.c over a Python dict keyed on the whole digest.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import dedup_cases as dc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "nydus-snapshotter_amd", "csrc")
+NEW, INTRA, DICT = 0, 1, 2
+NONE = 0xFFFFFFFF
+DEC = np.dtype([("kind", "<u4"), ("index", "<u4"), ("ref", "<u8"), ("blob_index", "<u4"),
+                ("uncompressed_offset", "<u8")])
+FIELDS = ("kind", "ref", "index", "blob_index", "uncompressed_offset")
+
+
+def model_dedup(digests, lengths, dd=(), ds=(), db=(), di=(), duoff=None, align=4096,
+                unusable=None):
+    """Stream-order dedup of one layer -> (decisions, layer stats as a dict).
+    1. chunk dict: the FIRST row of the digest answers; a hit iff its usize is
+       0 or the chunk's length; its inner blob gets the next real blob index at
+       its first hit.  unusable(row) -> True makes that row's answers misses.
+    2. else the layered dict (earlier NEW chunks, first insertion kept), same
+       length required: INTRA, copying that chunk's index / blob / offset.
+    3. else NEW: next index, own blob allocated at the first NEW chunk, offset
+       = running offset, which advances by the length rounded up to align."""
+    gdict, layered, real = {}, {}, {}
+    for j in range(len(ds)):
+        gdict.setdefault(bytes(dd[j]), j)
+    out = np.zeros(len(lengths), DEC)
+    own, blobs, new, cur, nbytes = NONE, 0, 0, 0, 0
+    for i, size in enumerate(int(x) for x in lengths):
+        key = bytes(digests[i])
+        e = gdict.get(key)
+        if e is not None and not (unusable and unusable(e)) and int(ds[e]) in (0, size):
+            if int(db[e]) not in real:
+                real[int(db[e])], blobs = blobs, blobs + 1
+            out[i] = (DICT, di[e], e, real[int(db[e])], 0 if duoff is None else duoff[e])
+            continue
+        f = layered.get(key)
+        if f is not None and int(lengths[f]) == size:
+            out[i] = (INTRA, out[f]["index"], f, own, out[f]["uncompressed_offset"])
+            continue
+        if own == NONE:
+            own, blobs = blobs, blobs + 1
+        out[i] = (NEW, new, i, own, cur)
+        new, nbytes, cur = new + 1, nbytes + size, (cur + size + align - 1) // align * align
+        layered.setdefault(key, i)
+    kinds = out["kind"]
+    stats = {"chunks": len(out), "new_chunks": new, "intra_chunks": int((kinds == INTRA).sum()),
+             "dict_chunks": int((kinds == DICT).sum()), "new_bytes": nbytes, "own_blob_index": own,
+             "blobs": blobs, "uncompressed_size": cur}
+    return out, stats
+
+
+def expect(case, unusable=None, uoff=True):
+    dd, ds, db, di, duoff, _ = case.dict
+    return model_dedup(case.digests, case.lengths, dd, ds, db, di, duoff if uoff else None,
+                       case.align, unusable)
+
+
+def all_cases():
+    """Every case the GPU matrix runs, as (id, getter arguments)."""
+    out = []
+    for align in (4096, 1):
+        for n in dc.ALL_N:
+            for wd in (False, True):
+                out.append(("mixed", n, align, wd, False))
+        for n in dc.PATH_N["small"]:
+            out.append(("mixed", n, align, True, True))
+        for n in dc.WHOLE_N:
+            for kind in ("hot", "distinct", "all_dict"):
+                out.append((kind, n, align, kind == "all_dict", False))
+    return out
+
+
+def case_id(a):
+    return f"{a[0]}-{a[1]}-a{a[2]}" + ("-dict" if a[3] else "") + ("-many" if a[4] else "")
+
+
+# ---- oracle vs model, and what each class was built for ------------------------
+
+def check_classes(case, dec):
+    n, cl, dg, ln = case.n, case.classes, case.digests, case.lengths
+    kind, ref = dec["kind"], dec["ref"].astype(np.int64)
+    full = n >= 64 and case.name.startswith("mixed")
+    if full:
+        want = {"tagchain", "bucketchain", "slotchain", "tagff", "sizerule", "hot", "lengths"}
+        if case.m:
+            want |= {"dict_tagchain", "dict_duprow", "dict_wildcard", "dict_sizerule", "dict_blobs"}
+        assert want <= set(cl), want - set(cl)
+    in_dict = {bytes(r) for r in case.dict[0]}
+    for g in cl.get("tagchain", []):
+        d = dg[g]
+        assert (d[:, :16] == d[0, :16]).all()
+        k = len({bytes(x) for x in d})
+        assert 2 <= k <= min(48, n // 4) and len(g) > k and len(g) <= 64
+        near = d[0] != d[1]
+        assert near[31] and near.sum() == 1
+        assert np.array_equal(d[0], d[k]) and g[0] < g[1] < g[k]  # 0 before and after its twin
+        assert (kind[g] == NEW).any() and (kind[g] == INTRA).any()
+        for c in g[kind[g] == INTRA]:
+            assert np.array_equal(dg[ref[c]], dg[c]) and ref[c] < c and kind[ref[c]] == NEW
+    if full:
+        ks = sorted(len({bytes(x) for x in dg[g]}) for g in cl["tagchain"])
+        assert ks[0] == 2 and ks[-1] == min(48, n // 4)
+    for g in cl.get("bucketchain", []):
+        d = dg[g]
+        assert (d[:, :8] == d[0, :8]).all() and len({bytes(x) for x in d[:, 8:12]}) == len(g) >= 2
+        assert (kind[g] == NEW).all()
+    mask = dc.lds_mask(n)
+    for j, g in enumerate(cl.get("slotchain", [])):
+        slots = dc.home_slot(dg[g], mask)
+        assert (slots == slots[0]).all() and len({bytes(x) for x in dg[g][:, :8]}) == len(g)
+        if j == 0:
+            assert len(g) >= 8 and int(slots[0]) == mask - 2  # wraps to slot 0
+        assert (kind[g] == NEW).all()
+    for g in cl.get("tagff", []):
+        ff, fe = dg[g[0]], dg[g[1]]
+        assert ff[8:12].tobytes() == b"\xff" * 4 and fe[8:12].tobytes() == b"\xfe\xff\xff\xff"
+        assert np.array_equal(np.delete(ff, range(8, 12)), np.delete(fe, range(8, 12)))
+        for pair in (g[0::2], g[1::2]):  # both digests NEW once; their true duplicates INTRA
+            first = pair.min()
+            assert kind[first] == NEW
+            for c in pair[pair != first]:
+                assert kind[c] == INTRA and ref[c] == first
+    for g in cl.get("sizerule", []):
+        assert (dg[g] == dg[g[0]]).all()
+        if len(g) == 3:
+            assert tuple(ln[g]) == (dc.S1, dc.S2, dc.S2) and tuple(kind[g]) == (NEW, NEW, NEW)
+        else:
+            assert tuple(ln[g]) == (dc.S1, dc.S1, dc.S2, dc.S1)
+            assert tuple(kind[g]) == (NEW, INTRA, NEW, INTRA) and ref[g[1]] == ref[g[3]] == g[0]
+        tw = [dc.lds_thread_wave(n, int(c)) for c in g]
+        assert len({t for t, _ in tw}) == len(g)
+        if n >= 255:  # four waves of chunks or more
+            assert len({w for _, w in tw}) == len(g)
+    if full:
+        assert sorted(len(g) for g in cl["sizerule"]) == [3, 4]
+    for g in cl.get("hot", []):
+        assert (dg[g] == dg[g[0]]).all() and len(g) * 4 >= n
+        assert kind[g[0]] == NEW and (kind[g[1:]] == INTRA).all() and (ref[g[1:]] == g[0]).all()
+        if case.name.startswith("mixed"):
+            assert g[0] > 0
+    if full:
+        assert sorted(ln[cl["lengths"][0]]) == list(dc.EDGE_LENGTHS)
+        assert (kind[cl["lengths"][0]] == NEW).all()
+    if not case.m:
+        assert (kind != DICT).all()
+        return
+    dd, ds, db, di, duoff, n_blobs = case.dict
+    first_row = {}
+    for j in range(len(ds)):
+        first_row.setdefault(bytes(dd[j]), j)
+    for c in np.flatnonzero(kind == DICT):
+        assert ref[c] == first_row[bytes(dg[c])] and ds[ref[c]] in (0, ln[c])
+    for g in cl.get("dict_tagchain", []):
+        assert (kind[g] == DICT).all() and (dg[g][:, :16] == dg[g[0]][:16]).all()
+        assert len({bytes(x) for x in dg[g]}) >= 2
+    for g in cl.get("dict_duprow", []):
+        rows = [j for j in range(len(ds)) if bytes(dd[j]) == bytes(dg[g[0]])]
+        assert len(rows) == 2 and kind[g[0]] == DICT and ref[g[0]] == rows[0]
+        assert db[rows[0]] != db[rows[1]] and ds[rows[0]] == 0 and ln[g[0]] != 0  # the wildcard
+    for g in cl.get("dict_sizerule", []):
+        assert tuple(kind[g]) == (NEW, INTRA, DICT) and ref[g[1]] == g[0]
+    if full or case.name.startswith("alldict"):
+        refused = [c for c in range(n) if bytes(dg[c]) in in_dict and kind[c] != DICT]
+        hit = db[ref[kind == DICT]]
+        order = list(dict.fromkeys(int(b) for b in hit))
+        assert len(order) >= 12 and order != sorted(order)  # first hits not in blob-number order
+        assert set(int(b) for b in db) - set(order)         # and some blobs never hit
+        assert n_blobs > max(order)
+        if full:
+            assert refused  # a dict hit refused by the size rule
+    if case.name.startswith("alldict"):
+        assert (kind == DICT).all()
+
+
+@pytest.mark.parametrize("args", all_cases(), ids=case_id)
+def test_oracle_equals_model_and_classes_hold(args, oracle, capsys):
+    case = dc.get(*args)
+    dd, ds, db, di, duoff, _ = case.dict
+    exp, st = expect(case)
+    if case.m:
+        got, own = oracle.dedup(case.digests, case.lengths, dd, ds, db, di, case.align, duoff)
+    else:
+        got, own = oracle.dedup(case.digests, case.lengths, align=case.align)
+    for f in FIELDS:
+        bad = np.flatnonzero(got[f] != exp[f])
+        assert not len(bad), (f, bad[:8], got[f][bad[:8]], exp[f][bad[:8]])
+    assert (NONE if own is None else own) == st["own_blob_index"]
+    counts = {k: sum(len(g) for g in v) for k, v in case.classes.items()}
+    with capsys.disabled():  # the record of what each case holds, in every run
+        print(f"\n{case_id(args)}: classes {counts}; NEW {st['new_chunks']} INTRA {st['intra_chunks']} "
+              f"DICT {st['dict_chunks']}; blobs {st['blobs']}, size {st['uncompressed_size']:#x}", end="")
+    check_classes(case, exp)
+    # equal-bytes-8..15 groups stay short: the oracle's chain cost is quadratic in them
+    # (the hot digest is one key: found at the first probe)
+    keys = {}
+    for d in {bytes(x) for x in case.digests}:
+        keys[d[8:16]] = keys.get(d[8:16], 0) + 1
+    assert max(keys.values()) <= 64
+    if args[0] == "all_dict":
+        assert st["own_blob_index"] == NONE and st["new_chunks"] == 0
+    off = exp["uncompressed_offset"][exp["kind"] != DICT]
+    if args[0] == "distinct" and case.n == 256:  # the prefix ends exactly at 2^32
+        assert st["uncompressed_size"] == 1 << 32 and int(off.max()) == (1 << 32) - dc.CHUNK_SIZE
+    if args[0] in ("mixed", "distinct") and case.n >= 600:  # and passes it from here up
+        assert int(off.max()) > 1 << 32 and st["uncompressed_size"] > 1 << 32
+
+
+def test_unusable_rows_count_as_misses():
+    case = dc.get("mixed", 257, 4096, True)
+    base, _ = expect(case)
+    rows = sorted({int(r) for r in base["ref"][base["kind"] == DICT]})[:3]
+    exp, st = expect(case, unusable=lambda e: e in rows)
+    was = np.isin(base["ref"], rows) & (base["kind"] == DICT)
+    assert was.any() and (exp["kind"][was] != DICT).all()
+    assert (exp["kind"][~was] == DICT).sum() == st["dict_chunks"]
+
+
+def test_builder_is_deterministic():
+    for args in (("mixed", 257, 4096, True, False), ("mixed", 64, 1, True, True),
+                 ("all_dict", 256, 4096, True, False)):
+        a = dc.get(*args)
+        kind, n, align, wd, many = args
+        if kind == "mixed":
+            b = dc.build(n, with_dict=wd, align=align, seed=dc.SEED, many_blobs=many)
+            c = dc.build(n, with_dict=wd, align=align, seed=dc.SEED + 1, many_blobs=many)
+            assert not np.array_equal(a.digests, c.digests)
+        else:
+            b = dc.build_all_dict(n, align=align, seed=dc.SEED)
+        assert a is not b and np.array_equal(a.digests, b.digests) and np.array_equal(a.lengths, b.lengths)
+        for x, y in zip(a.dict, b.dict):
+            assert np.array_equal(x, y)
+        assert a.classes.keys() == b.classes.keys()
+        for k in a.classes:
+            assert all(np.array_equal(x, y) for x, y in zip(a.classes[k], b.classes[k]))
+
+
+def test_degenerate_sizes_build():
+    for n in (1, 2, 3, 7, 8, 11, 12, 16, 31):
+        for wd in (False, True):
+            case = dc.build(n, with_dict=wd, align=4096, seed=3)
+            assert case.n == n and case.lengths.min() >= 1 and case.digests.any(axis=1).all()
+            exp, _ = expect(case)
+            check_classes(case, exp)
+
+
+# ---- which kernel a call shape selects ------------------------------------------
+
+def _const(text, name):
+    m = re.search(r"constexpr\s+\w+\s+" + name + r"\s*=\s*(\d+)", text)
+    assert m, name
+    return int(m.group(1))
+
+
+def select_path(n, layers, grid_flag, dict_blobs):
+    """launch_dedup (csrc/dedup.hip) restated.  layers: None for a call without
+    layer_first (ngpu_dedup_device), else L.  The constants are read from the
+    sources: kSmallDedupChunks (4096) and kSmallDedupLayers (64) in common.hpp,
+    kLdsBlobs (1024) in dedup.hip, and the `n <= 256` of the dedup_small_lds<256>
+    launch in launch_dedup."""
+    with open(os.path.join(CSRC, "common.hpp")) as f:
+        common = f.read()
+    with open(os.path.join(CSRC, "dedup.hip")) as f:
+        dedup = f.read()
+    small_chunks, small_layers = _const(common, "kSmallDedupChunks"), _const(common, "kSmallDedupLayers")
+    lds_blobs = _const(dedup, "kLdsBlobs")
+    m = re.search(r"if \(n <= (\d+) && !wide\)\s*hipExtLaunchKernelGGL\(dedup_small_lds<(\d+)>", dedup)
+    assert m and m.group(1) == m.group(2)
+    narrow = int(m.group(1))
+    assert (small_chunks, small_layers, lds_blobs, narrow) == (4096, 64, 1024, 256)
+    assert "const bool small = !ws.grid_stages && n <= kSmallDedupChunks && L <= kSmallDedupLayers;" in dedup
+    assert "if (small && single && nbo <= kLdsBlobs)" in dedup
+    single, L = layers is None, 1 if layers is None else layers
+    small = not grid_flag and n <= small_chunks and L <= small_layers
+    if small and single and dict_blobs + 1 <= lds_blobs:
+        return "lds256" if n <= narrow else "lds1024"
+    return "small" if small else "grid"
+
+
+def test_call_shapes_select_their_paths():
+    for blobs in (0, dc.N_BLOBS):
+        for n in dc.PATH_N["lds256"]:
+            assert select_path(n, None, False, blobs) == "lds256"
+        for n in dc.PATH_N["lds1024"]:
+            assert select_path(n, None, False, blobs) == "lds1024"
+        for n in dc.PATH_N["small"]:
+            assert select_path(n, 1, False, blobs) == "small"
+            assert select_path(n, 3, False, blobs) == "small"
+        for n in dc.PATH_N["grid"]:
+            assert select_path(n, None, True, blobs) == "grid"
+            assert select_path(n, 3, True, blobs) == "grid"
+        for n in (4097, 6000):
+            assert select_path(n, None, False, blobs) == "grid"
+    for n in dc.PATH_N["small"]:  # more than 1023 dict blobs: one layer leaves the LDS kernel
+        assert select_path(n, None, False, dc.MANY_BLOBS) == "small"
+    assert select_path(64, None, False, 1023) == "lds256" and select_path(64, None, False, 1024) == "small"
+    assert select_path(64, 65, False, 0) == "grid"
+    for n in dc.WHOLE_N:
+        assert select_path(n, None, False, dc.N_BLOBS) in ("lds256", "lds1024")
