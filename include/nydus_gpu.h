@@ -842,6 +842,65 @@ int ngpu_check_stream(ngpu_engine *eng, ngpu_read_at_fn ra, void *ctx, uint64_t 
                       ngpu_dict *dict, const ngpu_check_options *opt, ngpu_check_report *report,
                       ngpu_check_bad *bad, uint64_t bad_cap);
 
+/* ---- Verity: the dm-verity hash tree of a block image (additive in ABI 7) ---
+ * tarfs's `nydus-image export --block --verity` appends a dm-verity hash tree
+ * to the exported disk image and prints the options that open it
+ * (pkg/tarfs/tarfs.go:548: --no-superblock --format=1 -s "" --hash=sha256
+ * --data-block-size=512 --hash-block-size=4096 --data-blocks N --hash-offset
+ * OFF ROOT).  Exactly that tree, as cryptsetup and the kernel's dm-verity
+ * define it: a digest is SHA-256 of a whole 512-byte data block or a whole
+ * 4096-byte hash block (empty salt); a hash block is up to 128 consecutive
+ * digests of the level below, zero padded; level i (0 = above the data) has
+ * ceil(data_blocks / 128^(i+1)) hash blocks; `levels` is the smallest L >= 0
+ * with (data_blocks - 1) >> (7 L) == 0; the tree is the levels top first,
+ * level 0 last; the root is the SHA-256 of the single top hash block, or of
+ * the one data block when levels == 0 (tree_bytes == 0 then).  Only the tree:
+ * the block image itself (`export --block`) is not produced here. */
+typedef struct {
+  uint64_t data_blocks; /* data_bytes / 512 */
+  uint64_t hash_offset; /* data_bytes rounded up to 4096: where the tree goes in the image file */
+  uint64_t tree_bytes;  /* 4096 x hash blocks of all levels */
+  uint32_t levels;
+  uint32_t reserved;
+  uint8_t root[32];     /* ngpu_verity_layout leaves it zero */
+} ngpu_verity_info;
+
+/* The geometry alone; no engine, no GPU.  NGPU_EINVAL unless data_bytes is a
+ * non-zero multiple of 512 below 2^62. */
+int ngpu_verity_layout(uint64_t data_bytes, ngpu_verity_info *out);
+
+/* The device stage: device pointers, async on `stream`, no host wait.  d_tree
+ * receives the tree_bytes of ngpu_verity_layout(data_bytes) -- every byte,
+ * the zero tail of each level's last hash block included: the caller clears
+ * nothing -- and d_root the 32-byte root.  One launch for the data blocks,
+ * one per level above them, one for the root.  d_data and d_tree must be
+ * 16-byte aligned (NGPU_EINVAL otherwise, and for a bad data_bytes); d_tree
+ * may be NULL when tree_bytes is 0.  The tree is always SHA-256, whatever the
+ * engine's digester; no workspace is used, and the engine lock is held for the
+ * enqueue only. */
+int ngpu_verity_device(ngpu_engine *eng, const void *d_data, uint64_t data_bytes, void *d_tree,
+                       void *d_root, void *stream);
+
+typedef struct {
+  uint32_t flags;        /* reserved, 0 */
+  uint32_t threads;      /* host reader threads; 0 -> min(16, cores) */
+  uint64_t window_bytes; /* staging window, rounded down to a multiple of 512;
+                            0 -> the engine's staging_bytes */
+} ngpu_verity_options;
+
+/* The host pipeline: the image's first data_bytes are read through `ra` (from
+ * several threads at once) into two pinned windows of the engine's staging
+ * pool, copied to HBM and hashed into the level-0 region of a tree kept in
+ * HBM while the host fills the other window; the upper levels run after the
+ * last window, and the tree comes back through the pinned windows and is
+ * handed to `w` in order (w may be NULL: only *info is wanted).  Returns with
+ * everything it took released.  NGPU_EINVAL: a bad data_bytes, or a window
+ * below 512 bytes; NGPU_EIO: the reader failed (or `w` did); NGPU_ENOMEM: the
+ * tree or the windows do not fit. */
+int ngpu_verity_image(ngpu_engine *eng, ngpu_read_at_fn ra, void *ctx, uint64_t data_bytes,
+                      const ngpu_verity_options *opt, ngpu_write_fn w, void *wctx,
+                      ngpu_verity_info *info);
+
 /* converter.Merge (convert_unix.go:560-666) -> tool.Merge (builder.go:220-294,
  * `nydus-image merge --prefetch-policy fs [--chunk-dict] [--parent-bootstrap]`):
  * per-layer bootstraps (the image.boot entries, lowest layer first) into the

@@ -26,6 +26,7 @@ ERRORS = {-1: "EINVAL", -2: "EHIP", -3: "ENOMEM", -4: "ETAR", -5: "EUNSUPP",
           -6: "ENODEV", -7: "EIO", -8: "EFORMAT", -9: "ENOTFOUND", -10: "ECANCELED",
           -11: "EDEVICE"}
 EINVAL, EUNSUPP, ENODEV, EFORMAT, ENOTFOUND, ECANCELED, EDEVICE = -1, -5, -6, -8, -9, -10, -11
+EIO = -7
 
 # PackOption.Compressor -> TOCEntry flag values (pkg/converter/types.go:22-31);
 # "" is nydus-image's default (zstd).
@@ -76,7 +77,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # ABI 7
            "ngpu_pack_engine", "ngpu_engine_counters_get", "ngpu_merge_ex2",
            # Check (additive in ABI 7)
-           "ngpu_check_device", "ngpu_check_image", "ngpu_check_stream"]
+           "ngpu_check_device", "ngpu_check_image", "ngpu_check_stream",
+           # Verity (additive in ABI 7)
+           "ngpu_verity_layout", "ngpu_verity_device", "ngpu_verity_image"]
 
 LAYER_STATS_DTYPE = np.dtype([("chunks", "<u8"), ("new_chunks", "<u8"), ("intra_chunks", "<u8"),
                               ("dict_chunks", "<u8"), ("new_bytes", "<u8"), ("own_blob_index", "<u4"),
@@ -167,6 +170,21 @@ CHECK_BAD_DTYPE = np.dtype([("blob_index", "<u4"), ("index", "<u4"), ("reason", 
                             ("uncompressed_size", "<u4"), ("compressed_offset", "<u8"),
                             ("expected", "u1", (32,)), ("got", "u1", (32,))])
 assert CHECK_BAD_DTYPE.itemsize == 88
+
+
+class NgpuVerityInfo(ctypes.Structure):
+    _fields_ = [("data_blocks", ctypes.c_uint64), ("hash_offset", ctypes.c_uint64),
+                ("tree_bytes", ctypes.c_uint64), ("levels", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("root", ctypes.c_uint8 * 32)]
+
+    def as_dict(self):
+        return {"data_blocks": self.data_blocks, "hash_offset": self.hash_offset,
+                "tree_bytes": self.tree_bytes, "levels": self.levels, "root": bytes(self.root).hex()}
+
+
+class NgpuVerityOptions(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32), ("threads", ctypes.c_uint32),
+                ("window_bytes", ctypes.c_uint64)]
 
 
 class NgpuError(RuntimeError):
@@ -290,6 +308,10 @@ def lib():
                                    vp, u64]
     L.ngpu_check_stream.argtypes = [vp, READ_AT_FN, vp, u64, vp, ctypes.POINTER(NgpuCheckOptions),
                                     ctypes.POINTER(NgpuCheckReport), vp, u64]
+    L.ngpu_verity_layout.argtypes = [u64, ctypes.POINTER(NgpuVerityInfo)]
+    L.ngpu_verity_device.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.ngpu_verity_image.argtypes = [vp, READ_AT_FN, vp, u64, ctypes.POINTER(NgpuVerityOptions), WRITE_FN,
+                                    vp, ctypes.POINTER(NgpuVerityInfo)]
     _lib = L
     return L
 
@@ -379,6 +401,26 @@ class _Sink:
     def reraise(self):
         if self.exc is not None:
             raise self.exc
+
+
+class _ArraySink:
+    """An ngpu_write_fn that fills a uint8 array in order, straight from the
+    library's buffer (no bytes object in between); the same fn / ctx / reraise
+    as _Sink."""
+
+    def __init__(self, arr):
+        self.arr, self.at, self.ctx = arr, 0, None
+
+        def fn(_ctx, buf, n):
+            if self.at + n > self.arr.size:
+                return 1
+            ctypes.memmove(self.arr.ctypes.data + self.at, buf, n)
+            self.at += n
+            return 0
+        self.fn = WRITE_FN(fn)
+
+    def reraise(self):
+        pass
 
 
 def blob_options(compressor: str = "", level: int = 0, threads: int = 0, digester: str = "blake3",
@@ -483,6 +525,30 @@ def _mem_reader(src):
         ctypes.memmove(buf, src.ctypes.data + off, n)
         return n
     return READ_AT_FN(ra)
+
+
+def verity_layout(data_bytes: int) -> dict:
+    """ngpu_verity_layout: the geometry of the dm-verity tree of a block image
+    of `data_bytes` (a non-zero multiple of 512); no GPU.  The root is zero."""
+    info = NgpuVerityInfo()
+    rc = lib().ngpu_verity_layout(data_bytes, ctypes.byref(info))
+    if rc:
+        raise NgpuError(rc, f"verity_layout: {data_bytes} bytes is not a non-zero multiple of 512")
+    return info.as_dict()
+
+
+def verity_label(info: dict) -> str:
+    """"<data blocks>,<hash offset>,sha256:<root>": how the reference records a
+    layer's dm-verity information (pkg/tarfs/tarfs.go:554)."""
+    return f"{info['data_blocks']},{info['hash_offset']},sha256:{info['root']}"
+
+
+def verity_options_line(info: dict) -> str:
+    """The line `nydus-image export --block --verity` prints and
+    pkg/tarfs/tarfs.go:548 parses."""
+    return ('dm-verity options: --no-superblock --format=1 -s "" --hash=sha256 --data-block-size=512 '
+            f"--hash-block-size=4096 --data-blocks {info['data_blocks']} "
+            f"--hash-offset {info['hash_offset']} {info['root']}")
 
 
 def rafs_dump(bootstrap: bytes) -> dict:
@@ -826,6 +892,58 @@ class Engine:
                                            ctypes.byref(opt), ctypes.byref(rep), _ptr(bad), max_bad),
                     "check_image")
         return self._check_report(rep, bad)
+
+    def verity_device(self, d_data: int, data_bytes: int, d_tree: int, d_root: int, stream: int = 0):
+        """ngpu_verity_device: the dm-verity tree of the image at d_data into
+        d_tree (verity_layout(data_bytes)["tree_bytes"] bytes, every one
+        written) and its root into d_root (32 bytes).  Async on `stream`."""
+        self._check(lib().ngpu_verity_device(self._h, self._vp(d_data), data_bytes, self._vp(d_tree),
+                                             self._vp(d_root), self._vp(stream)), "verity_device")
+
+    def verity_image(self, reader, data_bytes: int, dest=None, window_bytes: int = 0,
+                     threads: int = 0) -> dict:
+        """ngpu_verity_image: `reader` is a READ_AT_FN over the image; the tree
+        is written to `dest` (file-like or FdWriter; None: only the info)."""
+        sink = dest if isinstance(dest, _ArraySink) else _Sink(dest) if dest is not None else None
+        opt = NgpuVerityOptions(0, threads, window_bytes)
+        info = NgpuVerityInfo()
+        rc = lib().ngpu_verity_image(self._h, reader, None, data_bytes, ctypes.byref(opt),
+                                     sink.fn if sink else WRITE_FN(), sink.ctx if sink else None,
+                                     ctypes.byref(info))
+        if sink:
+            sink.reraise()
+        self._check(rc, "verity")
+        return info.as_dict()
+
+    def verity(self, data, window_bytes: int = 0, threads: int = 0, want_tree: bool = True):
+        """The dm-verity tree of a block image in host memory (bytes / numpy
+        buffer): (tree as a uint8 array, info dict); tree is None with
+        want_tree=False."""
+        src = _buf(data)
+        tree = np.empty(verity_layout(src.size)["tree_bytes"], np.uint8) if want_tree else None
+        dest = _ArraySink(tree) if want_tree else None
+        info = self.verity_image(_mem_reader(src), src.size, dest, window_bytes, threads)
+        if want_tree and dest.at != tree.size:
+            raise NgpuError(EDEVICE, f"verity: {dest.at} of {tree.size} tree bytes written")
+        return tree, info
+
+    def verity_file(self, path: str, append: bool = False, window_bytes: int = 0, threads: int = 0) -> dict:
+        """The dm-verity tree of the block image in `path` (its whole size, a
+        multiple of 512).  append=True writes zeros from the file's end up to
+        hash_offset and then the tree: the file `nydus-image export --block
+        --verity` leaves.  Returns the info dict."""
+        src = np.memmap(path, np.uint8, mode="r")
+        size = src.size
+        try:
+            if not append:
+                return self.verity_image(_mem_reader(src), size, None, window_bytes, threads)
+            lay = verity_layout(size)
+            with open(path, "r+b") as f:
+                f.seek(size)
+                f.write(bytes(lay["hash_offset"] - size))
+                return self.verity_image(_mem_reader(src), size, f, window_bytes, threads)
+        finally:
+            del src
 
     def dict_probe_device(self, d_digests: int, stride: int, n: int, d_hits: int, stream: int = 0):
         self._check(lib().ngpu_dict_probe_device(self._h, self._vp(d_digests), stride, n,

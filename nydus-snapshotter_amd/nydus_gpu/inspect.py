@@ -20,6 +20,10 @@ usage:
   python -m nydus_gpu.inspect --diff --tree A B  # exit 0 iff the trees match
   python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP] [--chunk-size N] [--digester D]
                                               # re-digest STREAM's chunks on the GPU; exit 1 if any is bad
+  python -m nydus_gpu.inspect --verity IMAGE [--append]
+                                              # the dm-verity tree of a block image; prints its options line
+  python -m nydus_gpu.inspect --verity-verify IMAGE --data-blocks N --hash-offset OFF ROOT
+                                              # recompute the tree; exit 1 naming the first hash block that differs
 FILE may be a bootstrap (image.boot) or a whole Pack output stream.
 
 `--check` (Engine.check, ngpu_check_stream) needs a GPU: every chunk record of
@@ -28,6 +32,14 @@ and compared with the record's digest; records of other blobs must resolve in
 the `--dict` chunk-dict bootstrap (without one they are counted as skipped).
 The digester, chunk size and RAFS version default to the stream's own; the
 report is printed as JSON.
+
+`--verity` (Engine.verity_file, ngpu_verity_image) needs a GPU: IMAGE is a block
+image (`nydus-image export --block`, a multiple of 512 bytes); the line printed
+is the one `export --block --verity` prints and pkg/tarfs/tarfs.go:548 parses,
+and `--append` leaves the file that command leaves (zeros up to the hash
+offset, then the tree).  `--verity-verify` hashes the first N 512-byte blocks
+of IMAGE again and compares the root with ROOT and the tree with the bytes at
+OFF, on the host.
 """
 from __future__ import annotations
 
@@ -144,6 +156,56 @@ def check(path: str, dict_path: str = None, chunk_size: int = 0, digester: str =
                 dct.release()
 
 
+def verity(path: str, append: bool = False) -> dict:
+    """Engine.verity_file of the block image in `path` on GPU 0 (the info dict)."""
+    from ._lib import Engine
+    with Engine(device=0) as eng:
+        return eng.verity_file(path, append=append)
+
+
+def verity_verify(path: str, data_blocks: int, hash_offset: int, root: str) -> list:
+    """Recompute the tree of the first data_blocks x 512 bytes of `path` on GPU
+    0 and compare it with ROOT and with the tree stored at hash_offset.  Returns
+    the findings (empty: all equal).  A differing hash block is named at the
+    lowest level that has one -- the block closest to the damage: a changed
+    data block changes its level-0 hash block and every block above it."""
+    from ._lib import Engine, verity_layout
+    lay = verity_layout(data_blocks * 512)
+    src = np.memmap(path, np.uint8, mode="r")
+    if hash_offset < data_blocks * 512 or hash_offset + lay["tree_bytes"] > src.size:
+        raise ValueError(f"{path}: {src.size} bytes do not hold {data_blocks} data blocks and a tree of "
+                         f"{lay['tree_bytes']} bytes at {hash_offset}")
+    with Engine(device=0) as eng:
+        tree, info = eng.verity(src[:data_blocks * 512])
+    out = []
+    if info["root"] != root.lower():
+        out.append(f"root differs: computed {info['root']}, expected {root.lower()}")
+    stored = src[hash_offset:hash_offset + lay["tree_bytes"]].reshape(-1, 4096)
+    bad = np.flatnonzero((tree.reshape(-1, 4096) != stored).any(axis=1))
+    if len(bad):
+        # level sizes, level 0 first; the tree holds the top level first
+        sizes, n = [], data_blocks
+        for _ in range(lay["levels"]):
+            n = -(-n // 128)
+            sizes.append(n)
+        first, at = {}, 0
+        for lvl in reversed(range(len(sizes))):
+            first[lvl] = at
+            at += sizes[lvl]
+        for lvl in range(len(sizes)):
+            b = bad[(bad >= first[lvl]) & (bad < first[lvl] + sizes[lvl])]
+            if len(b):
+                t = int(b[0])
+                j = t - first[lvl]
+                span = 128 ** (lvl + 1)
+                out.append(f"hash block {t} (level {lvl}, block {j} of the level, file offset "
+                           f"{hash_offset + 4096 * t}) differs: it covers data blocks "
+                           f"{j * span}..{min(data_blocks, (j + 1) * span) - 1}; "
+                           f"{len(bad)} hash block(s) differ in all")
+                break
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nydus_gpu.inspect")
     ap.add_argument("files", nargs="*")
@@ -151,6 +213,11 @@ def main(argv=None) -> int:
     ap.add_argument("--dict", metavar="BOOTSTRAP", help="--check: chunk-dict bootstrap for DICT records")
     ap.add_argument("--chunk-size", type=lambda x: int(x, 0), default=0, help="--check: engine chunk size")
     ap.add_argument("--digester", choices=("blake3", "sha256"), help="--check: engine digester")
+    ap.add_argument("--verity", metavar="IMAGE", help="dm-verity tree of a block image on the GPU")
+    ap.add_argument("--append", action="store_true", help="--verity: append the tree to IMAGE at its hash offset")
+    ap.add_argument("--verity-verify", metavar="IMAGE", help="recompute IMAGE's tree and compare (ROOT follows)")
+    ap.add_argument("--data-blocks", type=int, help="--verity-verify: 512-byte data blocks")
+    ap.add_argument("--hash-offset", type=int, help="--verity-verify: where the tree starts in IMAGE")
     ap.add_argument("--diff", action="store_true", help="compare the chunk sets of two files")
     ap.add_argument("--tree", action="store_true", help="the inode tree instead of the chunk set")
     args = ap.parse_args(argv)
@@ -167,6 +234,27 @@ def main(argv=None) -> int:
         json.dump(rep, sys.stdout, indent=1)
         print()
         return 1 if rep["bad"] else 0
+    if args.verity or args.verity_verify:
+        try:
+            import torch  # noqa: F401  (one HIP runtime per process: before the library)
+        except ImportError:
+            pass
+        from ._lib import verity_options_line
+        try:
+            if args.verity:
+                print(verity_options_line(verity(args.verity, args.append)))
+                return 0
+            if args.data_blocks is None or args.hash_offset is None or len(args.files) != 1:
+                ap.error("--verity-verify takes --data-blocks N --hash-offset OFF ROOT")
+            found = verity_verify(args.verity_verify, args.data_blocks, args.hash_offset, args.files[0])
+        except (NgpuError, ValueError, OSError) as e:
+            print(f"verity: {e}", file=sys.stderr)
+            return 2
+        for line in found:
+            print(line)
+        if not found:
+            print(f"verity ok: {args.data_blocks} data blocks, root {args.files[0].lower()}")
+        return 1 if found else 0
     if not args.files:
         ap.error("no file given")
     if args.tree:
