@@ -901,6 +901,96 @@ int ngpu_verity_image(ngpu_engine *eng, ngpu_read_at_fn ra, void *ctx, uint64_t 
                       const ngpu_verity_options *opt, ngpu_write_fn w, void *wctx,
                       ngpu_verity_info *info);
 
+/* ---- Verity verify: an image against its STORED tree (additive in ABI 7) ----
+ * What the kernel's dm-verity and `veritysetup verify` decide, for every block
+ * at once and with a verdict per block.  The inputs are the data, the stored
+ * tree and a trusted 32-byte root; the geometry is ngpu_verity_layout's and
+ * comes from data_bytes alone -- nothing read from the image sizes or
+ * addresses anything.  With first[l] the tree block at which level l starts:
+ *   - data block i is bad iff SHA-256 of its 512 bytes differs from the 32
+ *     stored bytes at tree offset first[0] * 4096 + 32 i (levels == 0: from
+ *     the root);
+ *   - tree block t = first[l] + j has a bad hash iff SHA-256 of its 4096
+ *     stored bytes differs from the 32 stored bytes at first[l + 1] * 4096 +
+ *     32 j; the top block (t == 0) is compared with the root;
+ *   - level l has a bad spare area iff a byte of its last hash block after
+ *     that block's last digest is not zero (libcryptsetup refuses such a
+ *     tree, "Spare area is not zeroed", even when every hash is consistent).
+ * The image verifies iff none occurs, which holds iff the rebuilt tree equals
+ * the stored one and its root is the given root.  Every stored block is
+ * checked against its stored parent, so no level waits for another and a
+ * finding stays where the damage is: one flipped data byte is one bad data
+ * block and no bad hash block; a flipped byte in digest slot s of level-0
+ * block j is tree block first[0] + j (bad hash) and data block 128 j + s.
+ *
+ * The device calls: device pointers, async on `stream`, no host wait, no
+ * workspace, the engine lock held for the enqueue only.  d_data and d_tree
+ * must be 16-byte aligned, bitmaps and counts 8-byte aligned; `root` is host
+ * memory, read before the call returns; d_tree may be NULL when tree_bytes is
+ * 0.  Every word of a bitmap is written (zero words and the zero tail bits of
+ * the last word too: the caller clears nothing), and the counts are zeroed on
+ * `stream` first.  NGPU_EINVAL, with nothing launched: a misaligned or missing
+ * pointer, a bad data_bytes, first_block + n_blocks above data_blocks, or more
+ * blocks than one launch takes.  n_blocks == 0, or a tree call when
+ * tree_bytes is 0, only zeroes the counts. */
+
+/* All stored hash blocks of all levels in one launch: bit t of word t / 64 is
+ * set iff tree block t has a bad hash. */
+int ngpu_verity_verify_tree_device(ngpu_engine *eng, uint64_t data_bytes, const void *d_tree,
+                                   const uint8_t root[32] /* host */,
+                                   uint64_t *d_tree_bitmap /* (tree_blocks + 63) / 64 words */,
+                                   uint64_t *d_counts /* [0] bad-hash blocks, [1] spare mask: bit l = level l */,
+                                   void *stream);
+/* Data blocks [first_block, first_block + n_blocks) of the image, at d_data,
+ * against the stored level 0 in d_tree (the whole tree, as stored): bit k of
+ * word k / 64 is set iff data block first_block + k is bad. */
+int ngpu_verity_verify_data_device(ngpu_engine *eng, const void *d_data, uint64_t first_block,
+                                   uint64_t n_blocks, uint64_t data_bytes, const void *d_tree,
+                                   const uint8_t root[32] /* host */,
+                                   uint64_t *d_bitmap /* (n_blocks + 63) / 64 words, window-relative */,
+                                   uint64_t *d_count /* 1 word */, void *stream);
+
+typedef struct {
+  uint64_t data_blocks, tree_blocks, levels;
+  uint64_t bad_data;  /* bad data blocks */
+  uint64_t bad_hash;  /* tree blocks with a bad hash */
+  uint64_t bad_spare; /* levels with a bad spare area */
+  uint64_t bad;       /* all findings, listed or not: the image verifies iff 0 */
+  uint64_t bytes;     /* data and tree bytes hashed on the GPU */
+} ngpu_verity_report;
+enum {
+  NGPU_VERITY_BAD_DATA = 1, /* a data block does not hash to its stored level-0 digest */
+  NGPU_VERITY_BAD_HASH = 2, /* a stored hash block does not hash to its stored parent digest / the root */
+  NGPU_VERITY_BAD_SPARE = 3 /* the spare area of a level's last hash block is not zero */
+};
+typedef struct {
+  uint32_t reason;
+  uint32_t level;            /* of a tree block (0 = above the data); 0 for a data block */
+  uint64_t block;            /* the data-block number, or the tree-block number */
+  uint64_t first_data_block; /* the data blocks it covers, inclusive; */
+  uint64_t last_data_block;  /* for a data block, the block itself */
+  uint64_t file_offset;      /* 512 * block, or hash_offset + 4096 * block */
+} ngpu_verity_bad;
+
+/* The host pipeline, shaped like ngpu_verity_image.  The stored tree is read
+ * from hash_offset through the pinned windows into HBM and checked in one
+ * launch; then the image's first data_bytes follow window by window (H2D, one
+ * launch against the tree in HBM) while the host fills the other window.  Only
+ * each window's bitmap and count come back, and the host scans a bitmap only
+ * when its count is not zero.  report->bad counts every finding;
+ * bad[0 .. min(bad, bad_cap)) lists the first ones in this order: tree
+ * findings in tree-block order (top first; a block's HASH entry before its
+ * SPARE entry), then data blocks ascending.  A finding never stops the run:
+ * 0 means it ran to its end (read the report).  Returns with everything it
+ * took released.  NGPU_EINVAL: a bad data_bytes, a window below 512 bytes,
+ * hash_offset below data_bytes, or hash_offset + tree_bytes wrapping;
+ * NGPU_EIO: the reader failed, a file that ends before the tree does included;
+ * NGPU_ENOMEM: the tree or the windows do not fit. */
+int ngpu_verity_verify_image(ngpu_engine *eng, ngpu_read_at_fn ra, void *ctx, uint64_t data_bytes,
+                             uint64_t hash_offset, const uint8_t root[32],
+                             const ngpu_verity_options *opt, ngpu_verity_report *report,
+                             ngpu_verity_bad *bad, uint64_t bad_cap);
+
 /* converter.Merge (convert_unix.go:560-666) -> tool.Merge (builder.go:220-294,
  * `nydus-image merge --prefetch-policy fs [--chunk-dict] [--parent-bootstrap]`):
  * per-layer bootstraps (the image.boot entries, lowest layer first) into the

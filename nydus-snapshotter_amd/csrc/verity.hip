@@ -21,6 +21,17 @@
 //     threads fill one pinned window while the GPU hashes the other into the
 //     level-0 region of a tree kept in HBM; the upper levels run after the
 //     last window and the tree comes back through the same windows.
+//   * Verify (ngpu_verity_verify_*): an image against its STORED tree.  Every
+//     stored block is compared with its stored parent slot, so no level waits
+//     for another: verity_verify_data (one lane per data block against the
+//     stored level 0) and verity_verify_tree (one lane per stored hash block,
+//     all levels in one launch, against the parent slot or the trusted root;
+//     the spare area of a level's last block ORed on the way).  A verdict is
+//     one bit: __ballot per wave64 -> bitmap word -> popcount into a counter,
+//     as check_digests does.  The geometry of a stored block is
+//     verity_verify_plan.hpp's, for the kernel and the host's findings alike.
+//     ngpu_verity_verify_image reads the tree into HBM first, then the data
+//     window by window; only bitmaps and counts come back.
 // Everything runs on the caller's stream, nothing on the null stream (DESIGN
 // §3, "The digest guard").
 #include <algorithm>
@@ -32,6 +43,7 @@
 #include "engine_internal.hpp"
 #include "sha256_core.hpp"
 #include "verity_plan.hpp"
+#include "verity_verify_plan.hpp"
 
 namespace ngpu {
 namespace {
@@ -77,6 +89,46 @@ __device__ __forceinline__ void sha_pad_block(uint32_t h[8]) {
   }
   h[0] += a; h[1] += b; h[2] += c; h[3] += d;
   h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+}
+
+// SHA-256 of the NB * 64 bytes at q into h (the working words, big-endian
+// values): per-lane 16-byte loads, the next 64 bytes in flight during the
+// rounds, then the constant padding block.  SPARE (the verify kernel on a
+// stored hash block): returns the OR of every word from byte 32 * used on,
+// taken from the registers the loads fill; 0 otherwise.  The verify kernels'
+// copy of verity_hash's hashing: folding the two into one body changed the
+// schedule and register count of verity_leaves / verity_level, whose measured
+// code stays as it is.
+template <int NB, bool SPARE>
+__device__ __forceinline__ uint32_t verity_digest(const u32x4 *__restrict__ q, uint32_t h[8],
+                                                  uint32_t used) {
+  h[0] = 0x6a09e667u; h[1] = 0xbb67ae85u; h[2] = 0x3c6ef372u; h[3] = 0xa54ff53au;
+  h[4] = 0x510e527fu; h[5] = 0x9b05688cu; h[6] = 0x1f83d9abu; h[7] = 0x5be0cd19u;
+  u32x4 pf0 = q[0], pf1 = q[1], pf2 = q[2], pf3 = q[3];
+  uint32_t w[16], spare = 0;
+  auto take = [&](uint32_t b) {  // 64-byte block b = digest slots 2 b and 2 b + 1
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      w[j] = bswap_words(pf0, j); w[4 + j] = bswap_words(pf1, j);
+      w[8 + j] = bswap_words(pf2, j); w[12 + j] = bswap_words(pf3, j);
+    }
+    if constexpr (SPARE) {
+      const u32x4 lo = pf0 | pf1, hi = pf2 | pf3;
+      spare |= 2 * b >= used ? lo.x | lo.y | lo.z | lo.w : 0u;
+      spare |= 2 * b + 1 >= used ? hi.x | hi.y | hi.z | hi.w : 0u;
+    }
+  };
+#pragma unroll 1
+  for (int b = 1; b < NB; ++b) {
+    take((uint32_t)b - 1);
+    q += 4;
+    pf0 = q[0]; pf1 = q[1]; pf2 = q[2]; pf3 = q[3];
+    sha_block(h, w);
+  }
+  take(NB - 1);
+  sha_block(h, w);
+  sha_pad_block<NB * 512>(h);
+  return spare;
 }
 
 // Lane i < n_in hashes the NB * 64 bytes at in + i * NB * 64 into out + 32 i;
@@ -145,6 +197,87 @@ __global__ __launch_bounds__(256) void verity_level(const uint8_t *__restrict__ 
   verity_hash<64>(in, n_in, out, n_out, vec);
 }
 
+// ---- Verify: the image against its stored tree ------------------------------
+// The trusted root as the eight words a lane would load from its 32 bytes; a
+// kernel argument, so nothing is allocated for it.
+struct VerityRoot {
+  uint32_t w[8];
+};
+
+// h (big-endian values) against 32 stored bytes loaded as two 16-byte words.
+__device__ __forceinline__ bool verity_differs(const uint32_t h[8], u32x4 a, u32x4 b) {
+  return ((bswap(h[0]) ^ a.x) | (bswap(h[1]) ^ a.y) | (bswap(h[2]) ^ a.z) | (bswap(h[3]) ^ a.w) |
+          (bswap(h[4]) ^ b.x) | (bswap(h[5]) ^ b.y) | (bswap(h[6]) ^ b.z) | (bswap(h[7]) ^ b.w)) != 0;
+}
+
+// The verdicts of a wave64: the ballot is bitmap word k / 64 for the wave's
+// first lane k (256 % 64 == 0), stored whole -- zero words and the zero tail
+// bits of lanes past n too, which must reach the ballot (they vote 0); a wave
+// wholly past n stores nothing.  A non-zero word adds its popcount with one
+// atomicAdd, so a clean image issues none.
+__device__ __forceinline__ void verity_verdict(bool bad, uint64_t k, uint64_t n,
+                                               uint64_t *__restrict__ bitmap,
+                                               unsigned long long *__restrict__ count) {
+  const uint64_t word = __ballot(bad);
+  if ((threadIdx.x & 63u) == 0 && k < n) {
+    bitmap[k >> 6] = word;
+    if (word) atomicAdd(count, (unsigned long long)__popcll(word));
+  }
+}
+
+// Lane k < n hashes the 512-byte data block at data + 512 k (verity_leaves'
+// work) and compares it with the stored 32 bytes at stored + 32 k, contiguous
+// across lanes; stored == nullptr (one data block, no tree): with the root.
+__global__ __launch_bounds__(256) void verity_verify_data(const uint8_t *__restrict__ data, uint64_t n,
+                                                          const uint8_t *__restrict__ stored,
+                                                          VerityRoot root, uint64_t *__restrict__ bitmap,
+                                                          unsigned long long *__restrict__ count) {
+  const uint64_t k = blockIdx.x * 256ull + threadIdx.x;
+  bool bad = false;
+  if (k < n) {
+    uint32_t h[8];
+    verity_digest<8, false>(reinterpret_cast<const u32x4 *>(data + k * kVerityDataBlock), h, 0);
+    u32x4 a = {root.w[0], root.w[1], root.w[2], root.w[3]};
+    u32x4 b = {root.w[4], root.w[5], root.w[6], root.w[7]};
+    if (stored) {
+      const u32x4 *s = reinterpret_cast<const u32x4 *>(stored + kVerityDigest * k);
+      a = s[0];
+      b = s[1];
+    }
+    bad = verity_differs(h, a, b);
+  }
+  verity_verdict(bad, k, n, bitmap, count);
+}
+
+// Lane t < G.tree_blocks hashes stored hash block t (verity_level's work) and
+// compares it with its stored parent slot, or the root for t == 0: every level
+// in one launch, and as every lane runs the same 65 compressions whatever its
+// level, a wave that holds two levels does not diverge.  A level's last block
+// also ORs its words past its last digest; non-zero sets bit `level` of
+// counts[1].
+__global__ __launch_bounds__(256) void verity_verify_tree(const uint8_t *__restrict__ tree, VerityGeom G,
+                                                          VerityRoot root, uint64_t *__restrict__ bitmap,
+                                                          unsigned long long *__restrict__ counts) {
+  const uint64_t t = blockIdx.x * 256ull + threadIdx.x;
+  bool bad = false;
+  if (t < G.tree_blocks) {
+    const VerityBlockLoc at = verity_locate(G, t);
+    uint32_t h[8];
+    const uint32_t spare = verity_digest<64, true>(
+        reinterpret_cast<const u32x4 *>(tree + t * kVerityHashBlock), h, at.used);
+    u32x4 a = {root.w[0], root.w[1], root.w[2], root.w[3]};
+    u32x4 b = {root.w[4], root.w[5], root.w[6], root.w[7]};
+    if (at.parent_off != kVerityNoParent) {
+      const u32x4 *s = reinterpret_cast<const u32x4 *>(tree + at.parent_off);
+      a = s[0];
+      b = s[1];
+    }
+    bad = verity_differs(h, a, b);
+    if (spare) atomicOr(&counts[1], 1ull << at.level);
+  }
+  verity_verdict(bad, t, G.tree_blocks, bitmap, &counts[0]);
+}
+
 constexpr uint64_t kMaxLanes = 0x7FFFFFFFull * 256;  // one launch's grid
 
 // n_in messages at `in` -> n_out digest slots at `out` on s (leaves: 512-byte
@@ -189,20 +322,68 @@ void info_of(const VerityPlan &P, ngpu_verity_info *out) {
   out->levels = P.levels;
 }
 
-// Everything one ngpu_verity_image call holds, released on every path.  The
-// windows are staging slots of the engine (staging_take / staging_give).
+VerityRoot root_words(const uint8_t root[32]) {
+  VerityRoot r;
+  memcpy(r.w, root, 32);
+  return r;
+}
+
+// The plan of an image one launch can take, or NGPU_EINVAL.
+int checked_plan(ngpu_engine *e, uint64_t data_bytes, VerityPlan *P) {
+  if (!verity_plan(data_bytes, P))
+    return fail(e, NGPU_EINVAL, "verity: %llu data bytes: not a non-zero multiple of 512 below 2^62",
+                (unsigned long long)data_bytes);
+  if (P->blocks[0] * kVerityFanout > kMaxLanes)
+    return fail(e, NGPU_EINVAL, "verity: %llu data blocks are more than one launch takes",
+                (unsigned long long)P->data_blocks);
+  return 0;
+}
+
+// Every stored hash block of the tree at d_tree: counts zeroed on s, then one
+// launch (none without a tree).  The caller holds e->mu.
+int enqueue_verify_tree(ngpu_engine *e, const VerityPlan &P, const uint8_t *d_tree, const uint8_t root[32],
+                        uint64_t *d_bitmap, uint64_t *d_counts, hipStream_t s) {
+  // on the caller's stream, never the null stream ("The digest guard")
+  HIP_TRY(e, hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), s));
+  if (!P.tree_blocks) return 0;
+  hipLaunchKernelGGL(verity_verify_tree, dim3((unsigned)((P.tree_blocks + 255) / 256)), dim3(256), 0, s,
+                     d_tree, verity_geom(P), root_words(root), d_bitmap, (unsigned long long *)d_counts);
+  HIP_TRY(e, hipGetLastError());
+  return 0;
+}
+
+// Data blocks [block0, block0 + n) at d against the stored level 0 of d_tree
+// (levels == 0: against the root).  block0 + n <= P.data_blocks, n <= kMaxLanes.
+int enqueue_verify_data(ngpu_engine *e, const VerityPlan &P, const uint8_t *d, uint64_t block0, uint64_t n,
+                        const uint8_t *d_tree, const uint8_t root[32], uint64_t *d_bitmap,
+                        uint64_t *d_count, hipStream_t s) {
+  HIP_TRY(e, hipMemsetAsync(d_count, 0, sizeof(uint64_t), s));
+  if (!n) return 0;
+  const uint8_t *stored =
+      P.levels ? d_tree + P.first[0] * kVerityHashBlock + kVerityDigest * block0 : nullptr;
+  hipLaunchKernelGGL(verity_verify_data, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, n, stored,
+                     root_words(root), d_bitmap, (unsigned long long *)d_count);
+  HIP_TRY(e, hipGetLastError());
+  return 0;
+}
+
+// Everything one ngpu_verity_image / ngpu_verity_verify_image call holds,
+// released on every path.  The windows are staging slots of the engine
+// (staging_take / staging_give).
 struct VerityBufs {
   ngpu_engine *e = nullptr;
   int device = 0;
   hipStream_t s = nullptr;
   ngpu_staging_buf win[2];
   hipEvent_t done[2] = {}, fence = nullptr;
-  uint8_t *d_tree = nullptr;  // tree_bytes, then the 32-byte root
+  uint8_t *d_tree = nullptr;  // tree_bytes, then the 32-byte root (verify: the verdict words)
+  uint64_t *h_res = nullptr;  // verify: the verdict words on the host, pinned
   ~VerityBufs() {
     DeviceGuard g(device);
     if (s) (void)hipStreamSynchronize(s);
     for (ngpu_staging_buf &b : win) staging_give(e, b);
     if (d_tree) (void)hipFree(d_tree);
+    if (h_res) (void)hipHostFree(h_res);
     for (hipEvent_t ev : {done[0], done[1], fence})
       if (ev) (void)hipEventDestroy(ev);
     if (s) (void)hipStreamDestroy(s);
@@ -222,24 +403,48 @@ bool read_full(ngpu_read_at_fn ra, void *ctx, uint8_t *dst, uint64_t n, uint64_t
 
 constexpr uint64_t kReadPiece = 1ull << 20;  // what one reader thread takes at a time
 
+// The n bytes at `off` of the reader into h, in pieces, on up to `threads`
+// threads (the caller's among them).
+bool read_window(ngpu_read_at_fn ra, void *ctx, uint8_t *h, uint64_t n, uint64_t off, uint32_t threads) {
+  const uint64_t pieces = (n + kReadPiece - 1) / kReadPiece;
+  std::atomic<uint64_t> next{0};
+  std::atomic<bool> failed{false};
+  auto work = [&]() {
+    for (;;) {
+      const uint64_t q = next.fetch_add(1, std::memory_order_relaxed);
+      if (q >= pieces || failed.load(std::memory_order_relaxed)) return;
+      const uint64_t po = q * kReadPiece, pn = std::min(kReadPiece, n - po);
+      if (!read_full(ra, ctx, h + po, pn, off + po)) failed.store(true, std::memory_order_relaxed);
+    }
+  };
+  const uint32_t T = (uint32_t)std::min<uint64_t>(threads, pieces);
+  std::vector<std::thread> pool;
+  for (uint32_t t = 1; t < T; ++t) pool.emplace_back(work);
+  work();
+  for (auto &t : pool) t.join();
+  return !failed.load();
+}
+
+// opt with its defaults filled in; false: a window below one data block.
+bool verity_options(ngpu_engine *e, const ngpu_verity_options *opt, ngpu_verity_options *o) {
+  *o = ngpu_verity_options{};
+  if (opt) *o = *opt;
+  if (!o->window_bytes) o->window_bytes = e->cfg.staging_bytes;
+  o->window_bytes -= o->window_bytes % kVerityDataBlock;
+  if (!o->window_bytes) return false;
+  if (!o->threads) o->threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  o->threads = std::min(o->threads, 256u);
+  return true;
+}
+
 int verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_bytes,
                  const ngpu_verity_options *opt, ngpu_write_fn w, void *wctx,
                  ngpu_verity_info *info) {
   memset(info, 0, sizeof *info);
   VerityPlan P;
-  if (!verity_plan(data_bytes, &P))
-    return fail(e, NGPU_EINVAL, "verity: %llu data bytes: not a non-zero multiple of 512 below 2^62",
-                (unsigned long long)data_bytes);
-  if (P.blocks[0] * kVerityFanout > kMaxLanes)
-    return fail(e, NGPU_EINVAL, "verity: %llu data blocks are more than one launch takes",
-                (unsigned long long)P.data_blocks);
-  ngpu_verity_options o{};
-  if (opt) o = *opt;
-  if (!o.window_bytes) o.window_bytes = e->cfg.staging_bytes;
-  o.window_bytes -= o.window_bytes % kVerityDataBlock;
-  if (!o.window_bytes) return fail(e, NGPU_EINVAL, "verity: window below one 512-byte data block");
-  if (!o.threads) o.threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  o.threads = std::min(o.threads, 256u);
+  if (int rc = checked_plan(e, data_bytes, &P)) return rc;
+  ngpu_verity_options o;
+  if (!verity_options(e, opt, &o)) return fail(e, NGPU_EINVAL, "verity: window below one 512-byte data block");
   const uint64_t win = std::min(o.window_bytes, data_bytes);
   const uint64_t nwin = data_bytes / win + (data_bytes % win != 0);
   const int nbuf = nwin > 1 ? 2 : 1;
@@ -271,25 +476,7 @@ int verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_by
     if (wi >= (uint64_t)nbuf) HIP_TRY(e, hipEventSynchronize(B.done[k]));
     const uint64_t off = wi * win, n = std::min(win, data_bytes - off);
     uint8_t *h = (uint8_t *)B.win[k].h;
-    const uint64_t pieces = (n + kReadPiece - 1) / kReadPiece;
-    std::atomic<uint64_t> next{0};
-    std::atomic<bool> failed{false};
-    auto work = [&]() {
-      for (;;) {
-        const uint64_t q = next.fetch_add(1, std::memory_order_relaxed);
-        if (q >= pieces || failed.load(std::memory_order_relaxed)) return;
-        const uint64_t po = q * kReadPiece, pn = std::min(kReadPiece, n - po);
-        if (!read_full(ra, ctx, h + po, pn, off + po)) failed.store(true, std::memory_order_relaxed);
-      }
-    };
-    {
-      const uint32_t T = (uint32_t)std::min<uint64_t>(o.threads, pieces);
-      std::vector<std::thread> pool;
-      for (uint32_t t = 1; t < T; ++t) pool.emplace_back(work);
-      work();
-      for (auto &t : pool) t.join();
-    }
-    if (failed.load())
+    if (!read_window(ra, ctx, h, n, off, o.threads))
       return fail(e, NGPU_EIO, "verity: reading the image at [%llu, %llu) failed",
                   (unsigned long long)off, (unsigned long long)(off + n));
     HIP_TRY(e, hipMemcpyAsync(B.win[k].d, h, n, hipMemcpyHostToDevice, B.s));
@@ -339,6 +526,172 @@ int verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_by
   return 0;
 }
 
+// f(i) for every set bit lo <= i < hi of the bitmap, ascending, until it
+// returns false.
+template <class F>
+void each_set_bit(const uint64_t *words, uint64_t lo, uint64_t hi, F f) {
+  for (uint64_t i = lo; i < hi; ++i) {
+    const uint64_t rest = words[i >> 6] >> (i & 63);
+    if (!rest) {
+      i |= 63;
+      continue;
+    }
+    i += (uint64_t)__builtin_ctzll(rest);
+    if (i >= hi || !f(i)) return;
+  }
+}
+
+int verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_bytes,
+                        uint64_t hash_offset, const uint8_t root[32], const ngpu_verity_options *opt,
+                        ngpu_verity_report *rep, ngpu_verity_bad *bad, uint64_t bad_cap) {
+  memset(rep, 0, sizeof *rep);
+  VerityPlan P;
+  if (int rc = checked_plan(e, data_bytes, &P)) return rc;
+  if (hash_offset < data_bytes || hash_offset + P.tree_bytes < hash_offset)
+    return fail(e, NGPU_EINVAL, "verity: a tree of %llu bytes at %llu does not follow %llu data bytes",
+                (unsigned long long)P.tree_bytes, (unsigned long long)hash_offset,
+                (unsigned long long)data_bytes);
+  ngpu_verity_options o;
+  if (!verity_options(e, opt, &o)) return fail(e, NGPU_EINVAL, "verity: window below one 512-byte data block");
+  const VerityGeom G = verity_geom(P);
+  const uint64_t win = std::min(o.window_bytes, data_bytes);
+  const uint64_t nwin = data_bytes / win + (data_bytes % win != 0);
+  const uint64_t ntree = P.tree_bytes / win + (P.tree_bytes % win != 0);  // the tree goes through the windows first
+  const int nbuf = ntree + nwin > 1 ? 2 : 1;
+  // the verdict words, on the device behind the tree and pinned on the host:
+  // the tree's two counts and bitmap, then each window's count and bitmap
+  const uint64_t tw = (P.tree_blocks + 63) / 64, ww = (win / kVerityDataBlock + 63) / 64;
+  const uint64_t at[2] = {2 + tw, 2 + tw + 1 + ww}, words = 2 + tw + (uint64_t)nbuf * (1 + ww);
+
+  DeviceGuard dg(e->device);
+  VerityBufs B;
+  B.e = e;
+  B.device = e->device;
+  HIP_TRY(e, hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking));
+  HIP_TRY(e, hipEventCreateWithFlags(&B.fence, hipEventDisableTiming));
+  for (int k = 0; k < nbuf; ++k) {
+    HIP_TRY(e, hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
+    if (!staging_take(e, win, &B.win[k]))
+      return fail(e, NGPU_ENOMEM, "verity: two windows of %llu bytes", (unsigned long long)win);
+  }
+  if (hipMalloc((void **)&B.d_tree, P.tree_bytes + words * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    B.d_tree = nullptr;
+    return fail(e, NGPU_ENOMEM, "verity: a tree of %llu bytes does not fit the device",
+                (unsigned long long)P.tree_bytes);
+  }
+  if (hipHostMalloc((void **)&B.h_res, words * 8, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    B.h_res = nullptr;
+    return fail(e, NGPU_ENOMEM, "verity: %llu pinned verdict bytes", (unsigned long long)(words * 8));
+  }
+  uint64_t *d_res = (uint64_t *)(B.d_tree + P.tree_bytes);
+
+  uint64_t listed = 0;
+  auto add = [&](uint32_t reason, uint32_t level, uint64_t block, uint64_t lo, uint64_t hi, uint64_t off) {
+    if (listed < bad_cap) bad[listed++] = ngpu_verity_bad{reason, level, block, lo, hi, off};
+    return listed < bad_cap;
+  };
+  // The tree's findings, top first; a level's spare area belongs to its last
+  // block, so it follows that block's own entry and ends the level.
+  bool tree_seen = false;
+  auto harvest_tree = [&]() {
+    if (tree_seen) return;
+    tree_seen = true;
+    rep->bad_hash = B.h_res[0];
+    rep->bad_spare = (uint64_t)__builtin_popcountll(B.h_res[1]);
+    for (uint32_t l = P.levels; l-- > 0;) {
+      if (rep->bad_hash && listed < bad_cap)
+        each_set_bit(B.h_res + 2, P.first[l], P.first[l] + P.blocks[l], [&](uint64_t t) {
+          const VerityBlockLoc b = verity_locate(G, t);
+          return add(NGPU_VERITY_BAD_HASH, b.level, t, b.first_data, b.last_data,
+                     hash_offset + t * kVerityHashBlock);
+        });
+      if (B.h_res[1] >> l & 1) {
+        const uint64_t t = P.first[l] + P.blocks[l] - 1;
+        const VerityBlockLoc b = verity_locate(G, t);
+        add(NGPU_VERITY_BAD_SPARE, l, t, b.first_data, b.last_data, hash_offset + t * kVerityHashBlock);
+      }
+    }
+  };
+  // What window k holds verdicts of (n == 0: nothing), read once its `done`
+  // event or the whole stream has been waited for.
+  struct {
+    uint64_t block0 = 0, n = 0;
+  } held[2];
+  auto harvest = [&](int k) {
+    if (!held[k].n) return;
+    harvest_tree();  // enqueued before any window: it has landed too
+    const uint64_t *r = B.h_res + at[k];
+    rep->bad_data += r[0];
+    if (r[0] && listed < bad_cap)  // the bitmap is scanned only when the count says so
+      each_set_bit(r + 1, 0, held[k].n, [&](uint64_t i) {
+        const uint64_t b = held[k].block0 + i;
+        return add(NGPU_VERITY_BAD_DATA, 0, b, b, b, b * kVerityDataBlock);
+      });
+    held[k].n = 0;
+  };
+  // The next n bytes of the file into the next pinned window.
+  uint64_t fills = 0;
+  auto fill = [&](uint64_t off, uint64_t n, int *k) -> int {
+    *k = (int)(fills % (uint64_t)nbuf);
+    if (fills >= (uint64_t)nbuf) {
+      HIP_TRY(e, hipEventSynchronize(B.done[*k]));
+      harvest(*k);
+    }
+    ++fills;
+    if (!read_window(ra, ctx, (uint8_t *)B.win[*k].h, n, off, o.threads))
+      return fail(e, NGPU_EIO, "verity: reading the image at [%llu, %llu) failed", (unsigned long long)off,
+                  (unsigned long long)(off + n));
+    return 0;
+  };
+
+  // ---- the stored tree into HBM, then all of its blocks in one launch ------
+  for (uint64_t j = 0; j < ntree; ++j) {
+    const uint64_t off = j * win, n = std::min(win, P.tree_bytes - off);
+    int k;
+    if (int rc = fill(hash_offset + off, n, &k)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(B.d_tree + off, B.win[k].h, n, hipMemcpyHostToDevice, B.s));
+    HIP_TRY(e, hipEventRecord(B.done[k], B.s));
+  }
+  {
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = enqueue_verify_tree(e, P, B.d_tree, root, d_res + 2, d_res, B.s)) return rc;
+  }
+  HIP_TRY(e, hipEventRecord(B.fence, B.s));  // system-scope release before the host's copy
+  HIP_TRY(e, hipMemcpyAsync(B.h_res, d_res, (2 + tw) * 8, hipMemcpyDeviceToHost, B.s));
+
+  // ---- the image, window by window, against the tree in HBM ----------------
+  for (uint64_t wi = 0; wi < nwin; ++wi) {
+    const uint64_t off = wi * win, n = std::min(win, data_bytes - off), nb = n / kVerityDataBlock;
+    int k;
+    if (int rc = fill(off, n, &k)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(B.win[k].d, B.win[k].h, n, hipMemcpyHostToDevice, B.s));
+    {
+      std::lock_guard<std::mutex> g(e->mu);
+      if (int rc = enqueue_verify_data(e, P, (const uint8_t *)B.win[k].d, off / kVerityDataBlock, nb,
+                                       B.d_tree, root, d_res + at[k] + 1, d_res + at[k], B.s))
+        return rc;
+    }
+    HIP_TRY(e, hipEventRecord(B.fence, B.s));
+    HIP_TRY(e, hipMemcpyAsync(B.h_res + at[k], d_res + at[k], (1 + (nb + 63) / 64) * 8,
+                              hipMemcpyDeviceToHost, B.s));
+    HIP_TRY(e, hipEventRecord(B.done[k], B.s));
+    held[k].block0 = off / kVerityDataBlock;
+    held[k].n = nb;
+  }
+  HIP_TRY(e, hipStreamSynchronize(B.s));
+  for (uint64_t j = fills - std::min<uint64_t>(fills, (uint64_t)nbuf); j < fills; ++j)
+    harvest((int)(j % (uint64_t)nbuf));  // the older window first
+  harvest_tree();
+  rep->data_blocks = P.data_blocks;
+  rep->tree_blocks = P.tree_blocks;
+  rep->levels = P.levels;
+  rep->bad = rep->bad_data + rep->bad_hash + rep->bad_spare;
+  rep->bytes = data_bytes + P.tree_bytes;
+  return 0;
+}
+
 }  // namespace
 }  // namespace ngpu
 
@@ -382,6 +735,55 @@ int ngpu_verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t da
                       ngpu_verity_info *info) {
   if (!e || !ra || !info) return NGPU_EINVAL;
   const int rc = guarded([&]() -> int { return verity_image(e, ra, ctx, data_bytes, opt, w, wctx, info); });
+  if (rc == NGPU_ENOMEM) fail(e, rc, "verity: out of memory");
+  return rc;
+}
+
+int ngpu_verity_verify_tree_device(ngpu_engine *e, uint64_t data_bytes, const void *d_tree,
+                                   const uint8_t root[32], uint64_t *d_tree_bitmap, uint64_t *d_counts,
+                                   void *stream) {
+  if (!e || !root || !d_counts) return NGPU_EINVAL;
+  VerityPlan P;
+  if (int rc = checked_plan(e, data_bytes, &P)) return rc;
+  if (P.tree_bytes && (!d_tree || !d_tree_bitmap)) return fail(e, NGPU_EINVAL, "verity: no tree or no bitmap");
+  if (((uintptr_t)d_tree & 15) || ((uintptr_t)d_tree_bitmap & 7) || ((uintptr_t)d_counts & 7))
+    return fail(e, NGPU_EINVAL, "verity: d_tree must be 16-byte, the bitmap and counts 8-byte aligned");
+  std::lock_guard<std::mutex> g(e->mu);
+  DeviceGuard dg(e->device);
+  return enqueue_verify_tree(e, P, (const uint8_t *)d_tree, root, d_tree_bitmap, d_counts,
+                             (hipStream_t)stream);
+}
+
+int ngpu_verity_verify_data_device(ngpu_engine *e, const void *d_data, uint64_t first_block,
+                                   uint64_t n_blocks, uint64_t data_bytes, const void *d_tree,
+                                   const uint8_t root[32], uint64_t *d_bitmap, uint64_t *d_count,
+                                   void *stream) {
+  if (!e || !root || !d_count) return NGPU_EINVAL;
+  VerityPlan P;
+  if (int rc = checked_plan(e, data_bytes, &P)) return rc;
+  if (first_block > P.data_blocks || n_blocks > P.data_blocks - first_block)
+    return fail(e, NGPU_EINVAL, "verity: blocks [%llu, +%llu) are not within the image's %llu",
+                (unsigned long long)first_block, (unsigned long long)n_blocks,
+                (unsigned long long)P.data_blocks);
+  if (n_blocks &&(!d_data || !d_bitmap || (P.tree_bytes && !d_tree)))
+    return fail(e, NGPU_EINVAL, "verity: no data, no tree or no bitmap");
+  if (((uintptr_t)d_data & 15) || ((uintptr_t)d_tree & 15) || ((uintptr_t)d_bitmap & 7) ||
+      ((uintptr_t)d_count & 7))
+    return fail(e, NGPU_EINVAL,
+                "verity: d_data and d_tree must be 16-byte, the bitmap and count 8-byte aligned");
+  std::lock_guard<std::mutex> g(e->mu);
+  DeviceGuard dg(e->device);
+  return enqueue_verify_data(e, P, (const uint8_t *)d_data, first_block, n_blocks, (const uint8_t *)d_tree,
+                             root, d_bitmap, d_count, (hipStream_t)stream);
+}
+
+int ngpu_verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_bytes,
+                             uint64_t hash_offset, const uint8_t root[32], const ngpu_verity_options *opt,
+                             ngpu_verity_report *report, ngpu_verity_bad *bad, uint64_t bad_cap) {
+  if (!e || !ra || !root || !report || (bad_cap && !bad)) return NGPU_EINVAL;
+  const int rc = guarded([&]() -> int {
+    return verity_verify_image(e, ra, ctx, data_bytes, hash_offset, root, opt, report, bad, bad_cap);
+  });
   if (rc == NGPU_ENOMEM) fail(e, rc, "verity: out of memory");
   return rc;
 }

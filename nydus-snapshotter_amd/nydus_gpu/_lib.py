@@ -79,7 +79,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # Check (additive in ABI 7)
            "ngpu_check_device", "ngpu_check_image", "ngpu_check_stream",
            # Verity (additive in ABI 7)
-           "ngpu_verity_layout", "ngpu_verity_device", "ngpu_verity_image"]
+           "ngpu_verity_layout", "ngpu_verity_device", "ngpu_verity_image",
+           # Verity verify (additive in ABI 7)
+           "ngpu_verity_verify_tree_device", "ngpu_verity_verify_data_device", "ngpu_verity_verify_image"]
 
 LAYER_STATS_DTYPE = np.dtype([("chunks", "<u8"), ("new_chunks", "<u8"), ("intra_chunks", "<u8"),
                               ("dict_chunks", "<u8"), ("new_bytes", "<u8"), ("own_blob_index", "<u4"),
@@ -185,6 +187,20 @@ class NgpuVerityInfo(ctypes.Structure):
 class NgpuVerityOptions(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("threads", ctypes.c_uint32),
                 ("window_bytes", ctypes.c_uint64)]
+
+
+class NgpuVerityReport(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("data_blocks", "tree_blocks", "levels", "bad_data",
+                                               "bad_hash", "bad_spare", "bad", "bytes")]
+
+
+# ngpu_verity_bad.reason
+VERITY_BAD_DATA, VERITY_BAD_HASH, VERITY_BAD_SPARE = 1, 2, 3
+VERITY_REASONS = {1: "DATA", 2: "HASH", 3: "SPARE"}
+VERITY_BAD_DTYPE = np.dtype([("reason", "<u4"), ("level", "<u4"), ("block", "<u8"),
+                             ("first_data_block", "<u8"), ("last_data_block", "<u8"),
+                             ("file_offset", "<u8")])
+assert VERITY_BAD_DTYPE.itemsize == 40
 
 
 class NgpuError(RuntimeError):
@@ -312,6 +328,12 @@ def lib():
     L.ngpu_verity_device.argtypes = [vp, vp, u64, vp, vp, vp]
     L.ngpu_verity_image.argtypes = [vp, READ_AT_FN, vp, u64, ctypes.POINTER(NgpuVerityOptions), WRITE_FN,
                                     vp, ctypes.POINTER(NgpuVerityInfo)]
+    root32 = ctypes.c_char_p  # 32 bytes of host memory
+    L.ngpu_verity_verify_tree_device.argtypes = [vp, u64, vp, root32, vp, vp, vp]
+    L.ngpu_verity_verify_data_device.argtypes = [vp, vp, u64, u64, u64, vp, root32, vp, vp, vp]
+    L.ngpu_verity_verify_image.argtypes = [vp, READ_AT_FN, vp, u64, u64, root32,
+                                           ctypes.POINTER(NgpuVerityOptions),
+                                           ctypes.POINTER(NgpuVerityReport), vp, u64]
     _lib = L
     return L
 
@@ -541,6 +563,27 @@ def verity_label(info: dict) -> str:
     """"<data blocks>,<hash offset>,sha256:<root>": how the reference records a
     layer's dm-verity information (pkg/tarfs/tarfs.go:554)."""
     return f"{info['data_blocks']},{info['hash_offset']},sha256:{info['root']}"
+
+
+def parse_verity_label(label: str) -> dict:
+    """The inverse of verity_label: {"data_blocks", "hash_offset", "root"} of
+    "<data blocks>,<hash offset>,sha256:<root>" (ValueError otherwise)."""
+    parts = label.strip().split(",")
+    if len(parts) != 3 or not parts[2].startswith("sha256:"):
+        raise ValueError(f"not a dm-verity label (N,OFF,sha256:ROOT): {label!r}")
+    root = parts[2][len("sha256:"):].lower()
+    if len(root) != 64 or any(c not in "0123456789abcdef" for c in root):
+        raise ValueError(f"dm-verity label: the root is not 64 hex digits: {label!r}")
+    if not (parts[0].isascii() and parts[0].isdigit() and parts[1].isascii() and parts[1].isdigit()):
+        raise ValueError(f"dm-verity label: data blocks and hash offset are decimal numbers: {label!r}")
+    return {"data_blocks": int(parts[0]), "hash_offset": int(parts[1]), "root": root}
+
+
+def _root32(root) -> bytes:
+    r = bytes.fromhex(root) if isinstance(root, str) else bytes(root)
+    if len(r) != 32:
+        raise ValueError(f"a dm-verity root is 32 bytes, not {len(r)}")
+    return r
 
 
 def verity_options_line(info: dict) -> str:
@@ -942,6 +985,77 @@ class Engine:
                 f.seek(size)
                 f.write(bytes(lay["hash_offset"] - size))
                 return self.verity_image(_mem_reader(src), size, f, window_bytes, threads)
+        finally:
+            del src
+
+    def verity_verify_tree_device(self, data_bytes: int, d_tree: int, root, d_tree_bitmap: int,
+                                  d_counts: int, stream: int = 0):
+        """ngpu_verity_verify_tree_device: every stored hash block of the tree
+        at d_tree against its stored parent slot (the top one against `root`,
+        32 bytes or hex) in one launch.  Bit t of d_tree_bitmap: tree block t
+        has a bad hash; d_counts = [bad-hash blocks, spare mask (bit l = level
+        l)].  Async on `stream`."""
+        self._check(lib().ngpu_verity_verify_tree_device(
+            self._h, data_bytes, self._vp(d_tree), _root32(root), self._vp(d_tree_bitmap),
+            self._vp(d_counts), self._vp(stream)), "verity_verify_tree_device")
+
+    def verity_verify_data_device(self, d_data: int, first_block: int, n_blocks: int, data_bytes: int,
+                                  d_tree: int, root, d_bitmap: int, d_count: int, stream: int = 0):
+        """ngpu_verity_verify_data_device: data blocks [first_block, first_block
+        + n_blocks) at d_data against the stored level 0 of d_tree.  Bit k of
+        d_bitmap: block first_block + k is bad; d_count = their number.  Async
+        on `stream`."""
+        self._check(lib().ngpu_verity_verify_data_device(
+            self._h, self._vp(d_data), first_block, n_blocks, data_bytes, self._vp(d_tree), _root32(root),
+            self._vp(d_bitmap), self._vp(d_count), self._vp(stream)), "verity_verify_data_device")
+
+    def verity_verify_image(self, reader, data_bytes: int, hash_offset: int, root, max_bad: int = 64,
+                            window_bytes: int = 0, threads: int = 0) -> dict:
+        """ngpu_verity_verify_image: `reader` is a READ_AT_FN over a file that
+        holds data_bytes of data and, at hash_offset, their stored dm-verity
+        tree; `root` the trusted root (32 bytes or hex).  Returns the report as
+        a dict with a "bad_list" of at most max_bad findings: tree blocks top
+        first (HASH before SPARE), then data blocks ascending."""
+        opt = NgpuVerityOptions(0, threads, window_bytes)
+        rep = NgpuVerityReport()
+        bad = np.zeros(max_bad, VERITY_BAD_DTYPE)
+        self._check(lib().ngpu_verity_verify_image(self._h, reader, None, data_bytes, hash_offset,
+                                                   _root32(root), ctypes.byref(opt), ctypes.byref(rep),
+                                                   _ptr(bad), max_bad), "verity_verify")
+        d = {k: getattr(rep, k) for k, _ in rep._fields_}
+        d["bad_list"] = [{"reason": VERITY_REASONS.get(int(b["reason"]), int(b["reason"])),
+                          **{k: int(b[k]) for k in VERITY_BAD_DTYPE.names[1:]}}
+                         for b in bad[:min(rep.bad, max_bad)]]
+        return d
+
+    def verity_verify(self, data, tree, root, max_bad: int = 64, window_bytes: int = 0,
+                      threads: int = 0) -> dict:
+        """verity_verify_image of a block image and its stored tree in host
+        memory (bytes / numpy buffers)."""
+        src, tr = _buf(data), _buf(tree)
+        lay = verity_layout(src.size)
+        if tr.size != lay["tree_bytes"]:
+            raise ValueError(f"verity_verify: {tr.size} tree bytes, the image's tree has {lay['tree_bytes']}")
+
+        def ra(_ctx, buf, n, off):  # the tree right behind the data
+            part, at = (src, off) if off < src.size else (tr, off - src.size)
+            n = min(n, part.size - at)
+            if n <= 0:
+                return -1
+            ctypes.memmove(buf, part.ctypes.data + at, n)
+            return n
+        return self.verity_verify_image(READ_AT_FN(ra), src.size, src.size, root, max_bad, window_bytes,
+                                        threads)
+
+    def verity_verify_file(self, path: str, data_blocks: int, hash_offset: int, root, max_bad: int = 64,
+                           window_bytes: int = 0, threads: int = 0) -> dict:
+        """verity_verify_image of the file `export --block --verity` leaves:
+        data_blocks x 512 bytes of data and the tree at hash_offset.  A file
+        that ends before the tree does is an EIO."""
+        src = np.memmap(path, np.uint8, mode="r")
+        try:
+            return self.verity_verify_image(_mem_reader(src), data_blocks * 512, hash_offset, root, max_bad,
+                                            window_bytes, threads)
         finally:
             del src
 

@@ -24,6 +24,8 @@ usage:
                                               # the dm-verity tree of a block image; prints its options line
   python -m nydus_gpu.inspect --verity-verify IMAGE --data-blocks N --hash-offset OFF ROOT
                                               # recompute the tree; exit 1 naming the first hash block that differs
+  python -m nydus_gpu.inspect --verity-scan IMAGE (--data-blocks N --hash-offset OFF ROOT | --label N,OFF,sha256:ROOT)
+                                              # every block against the STORED tree; JSON report, exit 1 on findings
 FILE may be a bootstrap (image.boot) or a whole Pack output stream.
 
 `--check` (Engine.check, ngpu_check_stream) needs a GPU: every chunk record of
@@ -40,6 +42,15 @@ and `--append` leaves the file that command leaves (zeros up to the hash
 offset, then the tree).  `--verity-verify` hashes the first N 512-byte blocks
 of IMAGE again and compares the root with ROOT and the tree with the bytes at
 OFF, on the host.
+
+`--verity-scan` (Engine.verity_verify_file, ngpu_verity_verify_image) needs a
+GPU: the stored tree is read as it is and every data block and every stored
+hash block is checked against its stored parent digest (the top block against
+ROOT), as the kernel's dm-verity would on reading it; the spare area of each
+level's last hash block must be zero.  The report is printed as JSON with a
+`bad_list` that names each bad data block, and each bad tree block with its
+level and the data blocks it covers.  Exit 0: clean; 1: findings; 2: usage or
+I/O error.
 """
 from __future__ import annotations
 
@@ -206,6 +217,14 @@ def verity_verify(path: str, data_blocks: int, hash_offset: int, root: str) -> l
     return out
 
 
+def verity_scan(path: str, data_blocks: int, hash_offset: int, root: str, max_bad: int = 64) -> dict:
+    """Engine.verity_verify_file of `path` on GPU 0 (the report dict): every
+    data block and every stored hash block against the stored tree and ROOT."""
+    from ._lib import Engine
+    with Engine(device=0) as eng:
+        return eng.verity_verify_file(path, data_blocks, hash_offset, root, max_bad=max_bad)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nydus_gpu.inspect")
     ap.add_argument("files", nargs="*")
@@ -216,8 +235,12 @@ def main(argv=None) -> int:
     ap.add_argument("--verity", metavar="IMAGE", help="dm-verity tree of a block image on the GPU")
     ap.add_argument("--append", action="store_true", help="--verity: append the tree to IMAGE at its hash offset")
     ap.add_argument("--verity-verify", metavar="IMAGE", help="recompute IMAGE's tree and compare (ROOT follows)")
-    ap.add_argument("--data-blocks", type=int, help="--verity-verify: 512-byte data blocks")
-    ap.add_argument("--hash-offset", type=int, help="--verity-verify: where the tree starts in IMAGE")
+    ap.add_argument("--verity-scan", metavar="IMAGE",
+                    help="check every block of IMAGE against its stored tree on the GPU (ROOT or --label follows)")
+    ap.add_argument("--label", help="--verity-scan: N,OFF,sha256:ROOT in place of the three values")
+    ap.add_argument("--data-blocks", type=int, help="--verity-verify / --verity-scan: 512-byte data blocks")
+    ap.add_argument("--hash-offset", type=int,
+                    help="--verity-verify / --verity-scan: where the tree starts in IMAGE")
     ap.add_argument("--diff", action="store_true", help="compare the chunk sets of two files")
     ap.add_argument("--tree", action="store_true", help="the inode tree instead of the chunk set")
     args = ap.parse_args(argv)
@@ -230,6 +253,26 @@ def main(argv=None) -> int:
             rep = check(args.check, args.dict, args.chunk_size, args.digester)
         except (NgpuError, ValueError) as e:
             print(f"check: {e}", file=sys.stderr)
+            return 2
+        json.dump(rep, sys.stdout, indent=1)
+        print()
+        return 1 if rep["bad"] else 0
+    if args.verity_scan:
+        try:
+            import torch  # noqa: F401  (one HIP runtime per process: before the library)
+        except ImportError:
+            pass
+        from ._lib import parse_verity_label
+        some = args.data_blocks is not None or args.hash_offset is not None or bool(args.files)
+        three = args.data_blocks is not None and args.hash_offset is not None and len(args.files) == 1
+        if (args.label is not None) == some or (some and not three):
+            ap.error("--verity-scan takes --data-blocks N --hash-offset OFF ROOT, or --label LABEL")
+        try:
+            v = parse_verity_label(args.label) if args.label is not None else \
+                {"data_blocks": args.data_blocks, "hash_offset": args.hash_offset, "root": args.files[0]}
+            rep = verity_scan(args.verity_scan, v["data_blocks"], v["hash_offset"], v["root"])
+        except (NgpuError, ValueError, OSError) as e:
+            print(f"verity: {e}", file=sys.stderr)
             return 2
         json.dump(rep, sys.stdout, indent=1)
         print()

@@ -3,6 +3,8 @@
 
   python tools/verity_bench.py --device   # the tree of an image resident in HBM
   python tools/verity_bench.py --host     # Engine.verity of 2 GiB in host memory
+  python tools/verity_bench.py --verify-device   # verify against the build, images in HBM
+  python tools/verity_bench.py --verify-host     # Engine.verity_verify against rebuild-and-compare
 
 --device: a 4 GiB random image in HBM; `calls` back-to-back ngpu_verity_device
   calls between two HIP events, alternated for `rounds` rounds with the only
@@ -16,6 +18,11 @@
   compression, counting every compression of the tree.
 --host: Engine.verity on 2 GiB in host memory (the call ends synchronised),
   against a 16-thread hashlib build of the same tree timed in the same run.
+--verify-device: verify (ngpu_verity_verify_tree_device + _data_device) of 4 GiB
+  and 16 GiB images and their stored trees in HBM between two HIP events,
+  alternated round by round with ngpu_verity_device on the same bytes.
+--verify-host: Engine.verity_verify of 2 GiB in host memory, alternated with
+  Engine.verity plus the numpy compare of the tree (inspect.verity_verify's way).
 One JSON object per measurement on stdout."""
 import argparse
 import hashlib
@@ -217,10 +224,116 @@ def host_pipeline(reps):
     return out
 
 
+def spread(ts):
+    """The rounds of one measurement (rates() adds the median as "ms")."""
+    return {"rounds_ms": [round(x, 4) for x in ts], "spread_ms": round(max(ts) - min(ts), 4)}
+
+
+def verify_device(calls, rounds, big):
+    """Verify (ngpu_verity_verify_tree_device + _data_device) of an image and
+    its stored tree in HBM, alternated round by round with ngpu_verity_device
+    (the build) on the same bytes."""
+    out = []
+    s = torch.cuda.current_stream().cuda_stream
+    with nydus_gpu.Engine() as eng:
+        for nbytes, seed, c in ((4 * GiB, 7, calls), (16 * GiB, 9, max(2, calls // 4)))[:2 if big else 1]:
+            blocks = nbytes // 512
+            buf = random_device(nbytes, seed)
+            lay = nydus_gpu.verity_layout(nbytes)
+            tb = lay["tree_bytes"] // 4096
+            d_tree = torch.full((lay["tree_bytes"],), 0xFF, dtype=torch.uint8, device="cuda")
+            d_root = torch.zeros(32, dtype=torch.uint8, device="cuda")
+            d_bm = torch.full(((blocks + 63) // 64,), -1, dtype=torch.int64, device="cuda")
+            d_tbm = torch.full(((tb + 63) // 64,), -1, dtype=torch.int64, device="cuda")
+            d_cnt = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+            d_tcnt = torch.full((2,), -1, dtype=torch.int64, device="cuda")
+
+            def build():
+                eng.verity_device(buf.data_ptr(), nbytes, d_tree.data_ptr(), d_root.data_ptr(), stream=s)
+            build()
+            torch.cuda.synchronize()
+            root = d_root.cpu().numpy().tobytes()
+
+            def verify():
+                eng.verity_verify_tree_device(nbytes, d_tree.data_ptr(), root, d_tbm.data_ptr(),
+                                              d_tcnt.data_ptr(), stream=s)
+                eng.verity_verify_data_device(buf.data_ptr(), 0, blocks, nbytes, d_tree.data_ptr(), root,
+                                              d_bm.data_ptr(), d_cnt.data_ptr(), stream=s)
+            verify()
+            torch.cuda.synchronize()
+            assert not d_bm.any() and not d_tbm.any() and not d_cnt.any() and not d_tcnt.any(), \
+                "a clean image has findings"
+            # what is timed does check: one flipped data byte and one flipped digest are found
+            victim, slot = blocks - 12345, 777
+            at = sum(level_blocks(blocks)[1:]) * 4096 + 32 * slot  # level 0's stored digest of block `slot`
+            buf[victim * 512] ^= 1
+            d_tree[at] ^= 1
+            verify()
+            torch.cuda.synchronize()
+            assert d_cnt.tolist() == [2] and d_tcnt.tolist() == [1, 0], (d_cnt.tolist(), d_tcnt.tolist())
+            assert d_bm[victim // 64].item() == 1 << (victim % 64) and d_bm[slot // 64].item() == 1 << (slot % 64)
+            buf[victim * 512] ^= 1
+            d_tree[at] ^= 1
+            t = {"verify": [], "build": []}
+            for _ in range(rounds):
+                for name, fn in (("verify", verify), ("build", build)):
+                    t[name].append(timed(fn, c))
+            mv, mb = statistics.median(t["verify"]), statistics.median(t["build"])
+            out.append({"measure": f"verify_device_{nbytes // GiB}GiB", "image_bytes": nbytes,
+                        "tree_bytes": lay["tree_bytes"], "levels": lay["levels"], "calls_per_window": c,
+                        "launches": {"verify": 2, "build": lay["levels"] + 1},
+                        "verify": {**spread(t["verify"]), **rates(nbytes, mv)},
+                        "build": {**spread(t["build"]), **rates(nbytes, mb)},
+                        "verify_vs_build": round(mb / mv, 3)})
+            eng.device_status()
+            del buf, d_tree, d_bm, d_tbm
+            torch.cuda.empty_cache()
+    return out
+
+
+def verify_host(reps):
+    """Engine.verity_verify of a 2 GiB image and its tree in host memory,
+    alternated with the way there was before: Engine.verity (the tree rebuilt
+    and copied back) and the numpy compare of inspect.verity_verify."""
+    nbytes = 2 * GiB
+    data = np.random.default_rng(11).integers(0, 256, nbytes, dtype=np.uint8)
+    with nydus_gpu.Engine() as eng:
+        stored, info = eng.verity(data)  # warm-up: pins the two windows (kept in the engine's pool)
+        root = info["root"]
+        assert eng.verity_verify(data, stored, root)["bad"] == 0  # warm-up of the verify path
+        t = {"verify": [], "rebuild_and_compare": []}
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            rep = eng.verity_verify(data, stored, root)
+            t["verify"].append(time.perf_counter() - t0)
+            assert rep["bad"] == 0 and rep["bytes"] == nbytes + stored.size
+            t0 = time.perf_counter()
+            tree, got = eng.verity(data)
+            same = got["root"] == root and \
+                not (tree.reshape(-1, 4096) != stored.reshape(-1, 4096)).any(axis=1).any()
+            t["rebuild_and_compare"].append(time.perf_counter() - t0)
+            assert same
+        # one damaged data block: named exactly
+        data[512 * 4000000 + 5] ^= 1
+        rep = eng.verity_verify(data, stored, root)
+        assert rep["bad"] == 1 and rep["bad_list"][0]["block"] == 4000000, rep
+    row = {"measure": "verify_host_2GiB", "bytes": nbytes, "tree_bytes": int(stored.size)}
+    for k, ts in t.items():
+        row[k] = {"s": [round(x, 4) for x in ts], "median_s": round(statistics.median(ts), 4),
+                  "spread_s": round(max(ts) - min(ts), 4),
+                  "GBps_image": round(nbytes / statistics.median(ts) / 1e9, 2)}
+    row["verify_vs_rebuild"] = round(statistics.median(t["rebuild_and_compare"]) / statistics.median(t["verify"]), 3)
+    return [row]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--verify-device", action="store_true",
+                    help="verify of 4 GiB and 16 GiB images in HBM, alternated with the build")
+    ap.add_argument("--verify-host", action="store_true",
+                    help="Engine.verity_verify of 2 GiB in host memory against rebuild-and-compare")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3)
@@ -228,6 +341,14 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("verity_bench: no GPU (there is no CPU fallback)")
+    if args.verify_device:
+        for r in verify_device(args.calls, args.rounds, not args.no_16g):
+            print(json.dumps(r), flush=True)
+    if args.verify_host:
+        for r in verify_host(args.reps):
+            print(json.dumps(r), flush=True)
+    if args.verify_device or args.verify_host:
+        return
     if args.device or not args.host:
         for r in device_stage(args.calls, args.rounds, not args.no_16g):
             print(json.dumps(r), flush=True)
