@@ -12,24 +12,23 @@
 //     Only a wave with a non-zero word takes a second ballot, of the records
 //     the digest stage left unhashed, and a second atomicAdd if there are any
 //     (the error path).
-//   * ngpu_check_image: the host pipeline.  The bootstrap's chunk records are
-//     cut into windows of whole chunks (check_plan.hpp); a small thread pool
-//     reads each chunk from its blob and inflates it into a pinned window,
-//     the window goes to HBM with its chunk list and expected digests, and
-//     only the bitmap + counters come back -- the results too for a window
-//     with a bad record, to report the digest found.  Two windows: the host
-//     fills one while the GPU works on the other.
+//   * ngpu_check_image: the host pipeline (window_bufs.hpp, host_window.hpp).
+//     The bootstrap's chunk records are cut into windows of whole chunks
+//     (check_plan.hpp); the reader pool reads each chunk from its blob and
+//     inflates it into a pinned window, the window goes to HBM with its chunk
+//     list and expected digests, and only the bitmap + counters come back --
+//     the results too for a window with a bad record, to report the digest
+//     found.
 #include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
 #include "check_plan.hpp"
-#include "engine_internal.hpp"
+#include "host_window.hpp"
+#include "window_bufs.hpp"
 
 namespace ngpu {
 namespace {
@@ -80,48 +79,6 @@ __global__ __launch_bounds__(256) void check_digests(const ngpu_result *__restri
   }
 }
 
-// The big buffers of a window -- pinned host memory and as much HBM -- are a
-// staging slot of the engine (staging_take / staging_give, pack.hip: the pool
-// the streaming Packs keep theirs in; pinning 256 MiB costs more than copying
-// it), so a second Check, or a Pack after it, pins nothing.  Everything else
-// one Check call allocates is its own, released on every path.
-struct CheckBufs {
-  ngpu_engine *e = nullptr;
-  ngpu_staging_buf win[2];
-  int device = 0;
-  hipStream_t s = nullptr;
-  hipEvent_t done[2] = {}, fence = nullptr;
-  uint8_t *h_win[2] = {}, *d_win[2] = {};
-  ngpu_chunk *h_ch[2] = {}, *d_ch[2] = {};
-  uint8_t *h_exp[2] = {}, *d_exp[2] = {};
-  ngpu_result *d_out[2] = {};
-  uint64_t *d_verdict[2] = {}, *h_verdict[2] = {};  // [0, 2): counts, then the bitmap words
-  std::vector<void *> dev, host;
-  ~CheckBufs() {
-    DeviceGuard g(device);
-    if (s) (void)hipStreamSynchronize(s);
-    for (ngpu_staging_buf &b : win) staging_give(e, b);
-    for (void *p : dev) (void)hipFree(p);
-    for (void *p : host) (void)hipHostFree(p);
-    for (hipEvent_t ev : {done[0], done[1], fence})
-      if (ev) (void)hipEventDestroy(ev);
-    if (s) (void)hipStreamDestroy(s);
-  }
-  template <class T>
-  bool dmalloc(T **p, uint64_t bytes) {
-    if (hipMalloc((void **)p, bytes ? bytes : 64) != hipSuccess) return (void)hipGetLastError(), false;
-    dev.push_back(*p);
-    return true;
-  }
-  template <class T>
-  bool hmalloc(T **p, uint64_t bytes) {
-    if (hipHostMalloc((void **)p, bytes ? bytes : 64, hipHostMallocDefault) != hipSuccess)
-      return (void)hipGetLastError(), false;
-    host.push_back(*p);
-    return true;
-  }
-};
-
 struct Fail {
   uint64_t order;
   ngpu_check_bad b;
@@ -145,17 +102,6 @@ ngpu_check_bad bad_of(const RafsV6ChunkInfo &c, uint32_t reason) {
 // among the first `cap` overall.
 void keep(std::vector<Fail> &v, uint64_t cap, uint64_t order, const ngpu_check_bad &b) {
   if (v.size() < cap) v.push_back(Fail{order, b});
-}
-
-int read_full(const ngpu_check_blob &bl, uint8_t *dst, uint64_t n, uint64_t off) {
-  while (n) {
-    const int64_t r = bl.ra(bl.ctx, dst, n, off);
-    if (r <= 0 || (uint64_t)r > n) return NGPU_EIO;
-    dst += r;
-    off += (uint64_t)r;
-    n -= (uint64_t)r;
-  }
-  return 0;
 }
 
 // image.blob inside a layer stream, as a blob of its own
@@ -226,8 +172,7 @@ int check_image(ngpu_engine *e, const uint8_t *boot, uint64_t size, const ngpu_c
   if (o.window_bytes < chunk_size)
     return fail(e, NGPU_EINVAL, "check: window of %llu bytes below the chunk size 0x%x",
                 (unsigned long long)o.window_bytes, chunk_size);
-  if (!o.threads) o.threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  o.threads = std::min(o.threads, 256u);
+  o.threads = host_threads(o.threads);
   if (int rc = dict_check(e, dict)) return rc;
   if (recs.size() >= 0xFFFFFFFFull) return fail(e, NGPU_EFORMAT, "check: too many chunk records");
   rep->records = recs.size();
@@ -298,24 +243,22 @@ int check_image(ngpu_engine *e, const uint8_t *boot, uint64_t size, const ngpu_c
   std::vector<ngpu_dict_hit> hits;
   std::vector<ngpu_result> h_res;
   DeviceGuard dg_(e->device);
-  CheckBufs B;
-  B.e = e;
-  B.device = e->device;
-  HIP_TRY(e, hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking));
-  HIP_TRY(e, hipEventCreateWithFlags(&B.fence, hipEventDisableTiming));
+  WindowBufs B(e);
   const uint64_t vwords = 2 + (wcount + 63) / 64;
   const int nbuf = wins.size() > 1 ? 2 : (int)wins.size();
-  for (int k = 0; k < nbuf; ++k) {
-    HIP_TRY(e, hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
-    const bool got = staging_take(e, wbytes, &B.win[k]);
-    B.h_win[k] = (uint8_t *)B.win[k].h;
-    B.d_win[k] = (uint8_t *)B.win[k].d;
-    if (!got || !B.hmalloc(&B.h_ch[k], wcount * sizeof(ngpu_chunk)) ||
-        !B.dmalloc(&B.d_ch[k], wcount * sizeof(ngpu_chunk)) || !B.hmalloc(&B.h_exp[k], wcount * 32) ||
-        !B.dmalloc(&B.d_exp[k], wcount * 32) || !B.dmalloc(&B.d_out[k], wcount * sizeof(ngpu_result)) ||
-        !B.dmalloc(&B.d_verdict[k], vwords * 8) || !B.hmalloc(&B.h_verdict[k], vwords * 8))
-      return fail(e, NGPU_ENOMEM, "check: two windows of %llu bytes", (unsigned long long)wbytes);
-  }
+  if (int rc = B.open(nbuf, wbytes, "check")) return rc;
+  struct {  // what a window carries beside its bytes
+    ngpu_chunk *h_ch, *d_ch;
+    uint8_t *h_exp, *d_exp;
+    ngpu_result *d_out;
+    uint64_t *d_verdict, *h_verdict;  // [0, 2): counts, then the bitmap words
+  } W[2] = {};
+  for (int k = 0; k < nbuf; ++k)
+    if (!B.hmalloc(&W[k].h_ch, wcount * sizeof(ngpu_chunk)) ||
+        !B.dmalloc(&W[k].d_ch, wcount * sizeof(ngpu_chunk)) || !B.hmalloc(&W[k].h_exp, wcount * 32) ||
+        !B.dmalloc(&W[k].d_exp, wcount * 32) || !B.dmalloc(&W[k].d_out, wcount * sizeof(ngpu_result)) ||
+        !B.dmalloc(&W[k].d_verdict, vwords * 8) || !B.hmalloc(&W[k].h_verdict, vwords * 8))
+      return B.no_windows(wbytes, "check");
 
   std::vector<uint64_t> sent[2];  // per window buffer: the items on the GPU, chunk-list order
   std::vector<uint64_t> ords;
@@ -324,7 +267,7 @@ int check_image(ngpu_engine *e, const uint8_t *boot, uint64_t size, const ngpu_c
   auto finish = [&](int k) -> int {
     HIP_TRY(e, hipEventSynchronize(B.done[k]));
     const uint64_t n = sent[k].size();
-    const uint64_t *v = B.h_verdict[k];
+    const uint64_t *v = W[k].h_verdict;
     unhashed += v[1];
     if (!v[0]) return 0;
     ords.resize(v[0]);
@@ -335,7 +278,7 @@ int check_image(ngpu_engine *e, const uint8_t *boot, uint64_t size, const ngpu_c
     rep->bad += total;
     if (f_gpu.size() >= bad_cap) return 0;
     h_res.resize(n);
-    HIP_TRY(e, hipMemcpyAsync(h_res.data(), B.d_out[k], n * sizeof(ngpu_result), hipMemcpyDeviceToHost, B.s));
+    HIP_TRY(e, hipMemcpyAsync(h_res.data(), W[k].d_out, n * sizeof(ngpu_result), hipMemcpyDeviceToHost, B.s));
     HIP_TRY(e, hipStreamSynchronize(B.s));
     for (uint64_t q : ords) {
       const CheckItem &it = items[sent[k][q]];
@@ -353,35 +296,24 @@ int check_image(ngpu_engine *e, const uint8_t *boot, uint64_t size, const ngpu_c
     const CheckWindow &w = wins[wi];
     // fill: read + inflate the window's chunks on the pool
     std::vector<uint8_t> state(w.count, 0);  // 0 ok, 1 does not inflate, 2 reader failed
-    std::atomic<uint64_t> next{0};
-    auto work = [&]() {
-      std::vector<uint8_t> cbuf;
-      for (;;) {
-        const uint64_t q = next.fetch_add(1, std::memory_order_relaxed);
-        if (q >= w.count) return;
-        const CheckItem &it = items[w.first + q];
-        const RafsV6ChunkInfo &c = recs[it.order];
-        const ngpu_check_blob &bl = blobs[it.blob];
-        uint8_t *dst = B.h_win[k] + off[w.first + q];
-        if (!(c.flags & 1)) {
-          if (read_full(bl, dst, c.compressed_size, c.compressed_offset)) state[q] = 2;
-          continue;
-        }
-        cbuf.resize(c.compressed_size);
-        if (read_full(bl, cbuf.data(), c.compressed_size, c.compressed_offset))
-          state[q] = 2;
-        else if (decompress_chunk(btab[c.blob_index].compression_algo, cbuf.data(), c.compressed_size,
-                                  dst, c.uncompressed_size))
-          state[q] = 1;
+    uint8_t *h_win = (uint8_t *)B.win[k].h, *d_win = (uint8_t *)B.win[k].d;
+    // every chunk is tried; the first failing one in list order is named below
+    run_indexed(o.threads, w.count, [&, cbuf = std::vector<uint8_t>()](uint64_t q) mutable {
+      const CheckItem &it = items[w.first + q];
+      const RafsV6ChunkInfo &c = recs[it.order];
+      const ngpu_check_blob &bl = blobs[it.blob];
+      uint8_t *dst = h_win + off[w.first + q];
+      if (!(c.flags & 1)) {
+        if (!read_exact(bl.ra, bl.ctx, dst, c.compressed_size, c.compressed_offset)) state[q] = 2;
+        return;
       }
-    };
-    {
-      const uint32_t T = (uint32_t)std::min<uint64_t>(o.threads, w.count);
-      std::vector<std::thread> pool;
-      for (uint32_t t = 1; t < T; ++t) pool.emplace_back(work);
-      work();
-      for (auto &t : pool) t.join();
-    }
+      cbuf.resize(c.compressed_size);
+      if (!read_exact(bl.ra, bl.ctx, cbuf.data(), c.compressed_size, c.compressed_offset))
+        state[q] = 2;
+      else if (decompress_chunk(btab[c.blob_index].compression_algo, cbuf.data(), c.compressed_size,
+                                dst, c.uncompressed_size))
+        state[q] = 1;
+    });
     sent[k].clear();
     uint64_t bytes = 0;
     for (uint64_t q = 0; q < w.count; ++q) {
@@ -396,25 +328,22 @@ int check_image(ngpu_engine *e, const uint8_t *boot, uint64_t size, const ngpu_c
         continue;
       }
       const uint64_t g = sent[k].size();
-      B.h_ch[k][g] = ngpu_chunk{off[w.first + q], c.uncompressed_size, 0, 0};
-      memcpy(B.h_exp[k] + 32 * g, c.block_id, 32);
+      W[k].h_ch[g] = ngpu_chunk{off[w.first + q], c.uncompressed_size, 0, 0};
+      memcpy(W[k].h_exp + 32 * g, c.block_id, 32);
       sent[k].push_back(w.first + q);
       bytes += c.uncompressed_size;
     }
     const uint64_t n = sent[k].size();
     rep->bytes += bytes;
-    HIP_TRY(e, hipMemcpyAsync(B.d_win[k], B.h_win[k], w.bytes, hipMemcpyHostToDevice, B.s));
+    HIP_TRY(e, hipMemcpyAsync(d_win, h_win, w.bytes, hipMemcpyHostToDevice, B.s));
     if (n) {
-      HIP_TRY(e, hipMemcpyAsync(B.d_ch[k], B.h_ch[k], n * sizeof(ngpu_chunk), hipMemcpyHostToDevice, B.s));
-      HIP_TRY(e, hipMemcpyAsync(B.d_exp[k], B.h_exp[k], n * 32, hipMemcpyHostToDevice, B.s));
+      HIP_TRY(e, hipMemcpyAsync(W[k].d_ch, W[k].h_ch, n * sizeof(ngpu_chunk), hipMemcpyHostToDevice, B.s));
+      HIP_TRY(e, hipMemcpyAsync(W[k].d_exp, W[k].h_exp, n * 32, hipMemcpyHostToDevice, B.s));
     }
-    if (int rc = ngpu_check_device(e, B.d_win[k], w.bytes, B.d_ch[k], n, B.d_out[k], B.d_exp[k], 32,
-                                   B.d_verdict[k] + 2, B.d_verdict[k], B.s))
+    if (int rc = ngpu_check_device(e, d_win, w.bytes, W[k].d_ch, n, W[k].d_out, W[k].d_exp, 32,
+                                   W[k].d_verdict + 2, W[k].d_verdict, B.s))
       return rc;
-    HIP_TRY(e, hipEventRecord(B.fence, B.s));  // system-scope release before the host's copy
-    HIP_TRY(e, hipMemcpyAsync(B.h_verdict[k], B.d_verdict[k], (2 + (n + 63) / 64) * 8,
-                              hipMemcpyDeviceToHost, B.s));
-    HIP_TRY(e, hipEventRecord(B.done[k], B.s));
+    if (int rc = B.verdict_back(k, W[k].h_verdict, W[k].d_verdict, (2 + (n + 63) / 64) * 8)) return rc;
     e->check_windows.fetch_add(1, std::memory_order_relaxed);
   }
   for (size_t wi = wins.size() > 2 ? wins.size() - 2 : 0; wi < wins.size(); ++wi)
@@ -529,19 +458,17 @@ int ngpu_check_image(ngpu_engine *e, const void *bootstrap, uint64_t size,
                      const ngpu_check_options *opt, ngpu_check_report *report, ngpu_check_bad *bad,
                      uint64_t bad_cap) {
   if (!e || !bootstrap || !report || (n_blobs && !blobs) || (bad_cap && !bad)) return NGPU_EINVAL;
-  const int rc = guarded([&]() -> int {
+  return guarded_entry(e, "check", [&]() -> int {
     return check_image(e, (const uint8_t *)bootstrap, size, blobs, n_blobs, nullptr, nullptr, dict, opt,
                        report, bad, bad_cap);
   });
-  if (rc == NGPU_ENOMEM) fail(e, rc, "check: out of memory");
-  return rc;
 }
 
 int ngpu_check_stream(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t size, ngpu_dict *dict,
                       const ngpu_check_options *opt, ngpu_check_report *report, ngpu_check_bad *bad,
                       uint64_t bad_cap) {
   if (!e || !ra || !report || (bad_cap && !bad)) return NGPU_EINVAL;
-  const int rc = guarded([&]() -> int {
+  return guarded_entry(e, "check", [&]() -> int {
     LayerParts lp;
     if (int rc = locate_layer(ra, ctx, size, &lp)) return fail(e, rc, "check: %s", host_error());
     SubRange sr{ra, ctx, lp.data_off, lp.data_len};
@@ -549,8 +476,6 @@ int ngpu_check_stream(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t si
     return check_image(e, lp.boot.data(), lp.boot.size(), nullptr, 0, &lp, &own_src, dict, opt, report,
                        bad, bad_cap);
   });
-  if (rc == NGPU_ENOMEM) fail(e, rc, "check: out of memory");
-  return rc;
 }
 
 }  // extern "C"

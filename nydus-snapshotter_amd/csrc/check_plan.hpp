@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "host_window.hpp"
+
 namespace ngpu {
 
 // One chunk record to check: its uncompressed size (what it takes in a
@@ -60,16 +62,10 @@ inline bool check_plan_windows(const CheckItem *it, uint64_t n, uint64_t window,
 inline uint64_t check_decode_bitmap(const uint64_t *words, uint64_t n, uint64_t *out,
                                     uint64_t cap) {
   uint64_t total = 0;
-  for (uint64_t w = 0; w < (n + 63) / 64; ++w) {
-    uint64_t m = words[w];
-    if (w == n / 64 && (n & 63)) m &= (1ull << (n & 63)) - 1;
-    while (m) {
-      const int b = __builtin_ctzll(m);
-      m &= m - 1;
-      if (total < cap) out[total] = w * 64 + (uint64_t)b;
-      ++total;
-    }
-  }
+  each_set_bit(words, 0, n, [&](uint64_t i) {
+    if (total < cap) out[total] = i;
+    return ++total, true;
+  });
   return total;
 }
 

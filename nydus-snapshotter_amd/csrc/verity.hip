@@ -17,10 +17,10 @@
 //   Both write zeros to the digest slots between the last digest and the end
 //   of the level's last hash block, so every byte of the tree is written and
 //   the caller never clears it; lanes past that store nothing.
-//   * ngpu_verity_image: the host pipeline (shaped like Check's): reader
-//     threads fill one pinned window while the GPU hashes the other into the
-//     level-0 region of a tree kept in HBM; the upper levels run after the
-//     last window and the tree comes back through the same windows.
+//   * ngpu_verity_image: the host pipeline (window_bufs.hpp, host_window.hpp):
+//     the GPU hashes each window into the level-0 region of a tree kept in
+//     HBM; the upper levels run after the last window and the tree comes back
+//     through the same windows.
 //   * Verify (ngpu_verity_verify_*): an image against its STORED tree.  Every
 //     stored block is compared with its stored parent slot, so no level waits
 //     for another: verity_verify_data (one lane per data block against the
@@ -37,13 +37,13 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <thread>
 #include <vector>
 
-#include "engine_internal.hpp"
+#include "host_window.hpp"
 #include "sha256_core.hpp"
 #include "verity_plan.hpp"
 #include "verity_verify_plan.hpp"
+#include "window_bufs.hpp"
 
 namespace ngpu {
 namespace {
@@ -367,61 +367,17 @@ int enqueue_verify_data(ngpu_engine *e, const VerityPlan &P, const uint8_t *d, u
   return 0;
 }
 
-// Everything one ngpu_verity_image / ngpu_verity_verify_image call holds,
-// released on every path.  The windows are staging slots of the engine
-// (staging_take / staging_give).
-struct VerityBufs {
-  ngpu_engine *e = nullptr;
-  int device = 0;
-  hipStream_t s = nullptr;
-  ngpu_staging_buf win[2];
-  hipEvent_t done[2] = {}, fence = nullptr;
-  uint8_t *d_tree = nullptr;  // tree_bytes, then the 32-byte root (verify: the verdict words)
-  uint64_t *h_res = nullptr;  // verify: the verdict words on the host, pinned
-  ~VerityBufs() {
-    DeviceGuard g(device);
-    if (s) (void)hipStreamSynchronize(s);
-    for (ngpu_staging_buf &b : win) staging_give(e, b);
-    if (d_tree) (void)hipFree(d_tree);
-    if (h_res) (void)hipHostFree(h_res);
-    for (hipEvent_t ev : {done[0], done[1], fence})
-      if (ev) (void)hipEventDestroy(ev);
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
-bool read_full(ngpu_read_at_fn ra, void *ctx, uint8_t *dst, uint64_t n, uint64_t off) {
-  while (n) {
-    const int64_t r = ra(ctx, dst, n, off);
-    if (r <= 0 || (uint64_t)r > n) return false;
-    dst += r;
-    off += (uint64_t)r;
-    n -= (uint64_t)r;
-  }
-  return true;
-}
-
 constexpr uint64_t kReadPiece = 1ull << 20;  // what one reader thread takes at a time
 
 // The n bytes at `off` of the reader into h, in pieces, on up to `threads`
 // threads (the caller's among them).
 bool read_window(ngpu_read_at_fn ra, void *ctx, uint8_t *h, uint64_t n, uint64_t off, uint32_t threads) {
-  const uint64_t pieces = (n + kReadPiece - 1) / kReadPiece;
-  std::atomic<uint64_t> next{0};
   std::atomic<bool> failed{false};
-  auto work = [&]() {
-    for (;;) {
-      const uint64_t q = next.fetch_add(1, std::memory_order_relaxed);
-      if (q >= pieces || failed.load(std::memory_order_relaxed)) return;
-      const uint64_t po = q * kReadPiece, pn = std::min(kReadPiece, n - po);
-      if (!read_full(ra, ctx, h + po, pn, off + po)) failed.store(true, std::memory_order_relaxed);
-    }
-  };
-  const uint32_t T = (uint32_t)std::min<uint64_t>(threads, pieces);
-  std::vector<std::thread> pool;
-  for (uint32_t t = 1; t < T; ++t) pool.emplace_back(work);
-  work();
-  for (auto &t : pool) t.join();
+  run_indexed(threads, (n + kReadPiece - 1) / kReadPiece, [&](uint64_t q) {
+    if (failed.load(std::memory_order_relaxed)) return;
+    const uint64_t po = q * kReadPiece, pn = std::min(kReadPiece, n - po);
+    if (!read_exact(ra, ctx, h + po, pn, off + po)) failed.store(true, std::memory_order_relaxed);
+  });
   return !failed.load();
 }
 
@@ -432,8 +388,7 @@ bool verity_options(ngpu_engine *e, const ngpu_verity_options *opt, ngpu_verity_
   if (!o->window_bytes) o->window_bytes = e->cfg.staging_bytes;
   o->window_bytes -= o->window_bytes % kVerityDataBlock;
   if (!o->window_bytes) return false;
-  if (!o->threads) o->threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  o->threads = std::min(o->threads, 256u);
+  o->threads = host_threads(o->threads);
   return true;
 }
 
@@ -452,23 +407,13 @@ int verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_by
   uint8_t root[32];  // pageable target of an async copy on B.s: declared before B,
                      // whose destructor synchronises the stream on every path
   DeviceGuard dg(e->device);
-  VerityBufs B;
-  B.e = e;
-  B.device = e->device;
-  HIP_TRY(e, hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking));
-  HIP_TRY(e, hipEventCreateWithFlags(&B.fence, hipEventDisableTiming));
-  for (int k = 0; k < nbuf; ++k) {
-    HIP_TRY(e, hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
-    if (!staging_take(e, win, &B.win[k]))
-      return fail(e, NGPU_ENOMEM, "verity: two windows of %llu bytes", (unsigned long long)win);
-  }
-  if (hipMalloc((void **)&B.d_tree, P.tree_bytes + 64) != hipSuccess) {
-    (void)hipGetLastError();
-    B.d_tree = nullptr;
+  WindowBufs B(e);
+  if (int rc = B.open(nbuf, win, "verity")) return rc;
+  uint8_t *d_tree = nullptr;  // tree_bytes, then the 32-byte root
+  if (!B.dmalloc(&d_tree, P.tree_bytes + 64))
     return fail(e, NGPU_ENOMEM, "verity: a tree of %llu bytes does not fit the device",
                 (unsigned long long)P.tree_bytes);
-  }
-  uint8_t *d_root = B.d_tree + P.tree_bytes;
+  uint8_t *d_root = d_tree + P.tree_bytes;
 
   // ---- the image, window by window, into level 0 ---------------------------
   for (uint64_t wi = 0; wi < nwin; ++wi) {
@@ -483,14 +428,14 @@ int verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_by
     {
       std::lock_guard<std::mutex> g(e->mu);
       enqueue_leaves(P, (const uint8_t *)B.win[k].d, off / kVerityDataBlock, n / kVerityDataBlock,
-                     wi + 1 == nwin, B.d_tree, d_root, B.s);
+                     wi + 1 == nwin, d_tree, d_root, B.s);
       HIP_TRY(e, hipGetLastError());
     }
     HIP_TRY(e, hipEventRecord(B.done[k], B.s));
   }
   {
     std::lock_guard<std::mutex> g(e->mu);
-    enqueue_upper(P, B.d_tree, d_root, B.s);
+    enqueue_upper(P, d_tree, d_root, B.s);
     HIP_TRY(e, hipGetLastError());
   }
   HIP_TRY(e, hipEventRecord(B.fence, B.s));  // system-scope release before the host's copies
@@ -502,7 +447,7 @@ int verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_by
     auto issue = [&](uint64_t j) -> int {
       const int k = (int)(j % (uint64_t)nbuf);
       const uint64_t at = j * win;
-      HIP_TRY(e, hipMemcpyAsync(B.win[k].h, B.d_tree + at, std::min(win, P.tree_bytes - at),
+      HIP_TRY(e, hipMemcpyAsync(B.win[k].h, d_tree + at, std::min(win, P.tree_bytes - at),
                                 hipMemcpyDeviceToHost, B.s));
       HIP_TRY(e, hipEventRecord(B.done[k], B.s));
       return 0;
@@ -524,21 +469,6 @@ int verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_by
   info_of(P, info);
   memcpy(info->root, root, 32);
   return 0;
-}
-
-// f(i) for every set bit lo <= i < hi of the bitmap, ascending, until it
-// returns false.
-template <class F>
-void each_set_bit(const uint64_t *words, uint64_t lo, uint64_t hi, F f) {
-  for (uint64_t i = lo; i < hi; ++i) {
-    const uint64_t rest = words[i >> 6] >> (i & 63);
-    if (!rest) {
-      i |= 63;
-      continue;
-    }
-    i += (uint64_t)__builtin_ctzll(rest);
-    if (i >= hi || !f(i)) return;
-  }
 }
 
 int verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t data_bytes,
@@ -564,28 +494,16 @@ int verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t 
   const uint64_t at[2] = {2 + tw, 2 + tw + 1 + ww}, words = 2 + tw + (uint64_t)nbuf * (1 + ww);
 
   DeviceGuard dg(e->device);
-  VerityBufs B;
-  B.e = e;
-  B.device = e->device;
-  HIP_TRY(e, hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking));
-  HIP_TRY(e, hipEventCreateWithFlags(&B.fence, hipEventDisableTiming));
-  for (int k = 0; k < nbuf; ++k) {
-    HIP_TRY(e, hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
-    if (!staging_take(e, win, &B.win[k]))
-      return fail(e, NGPU_ENOMEM, "verity: two windows of %llu bytes", (unsigned long long)win);
-  }
-  if (hipMalloc((void **)&B.d_tree, P.tree_bytes + words * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    B.d_tree = nullptr;
+  WindowBufs B(e);
+  if (int rc = B.open(nbuf, win, "verity")) return rc;
+  uint8_t *d_tree = nullptr;  // tree_bytes, then the verdict words
+  uint64_t *h_res = nullptr;  // the verdict words on the host, pinned
+  if (!B.dmalloc(&d_tree, P.tree_bytes + words * 8))
     return fail(e, NGPU_ENOMEM, "verity: a tree of %llu bytes does not fit the device",
                 (unsigned long long)P.tree_bytes);
-  }
-  if (hipHostMalloc((void **)&B.h_res, words * 8, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    B.h_res = nullptr;
+  if (!B.hmalloc(&h_res, words * 8))
     return fail(e, NGPU_ENOMEM, "verity: %llu pinned verdict bytes", (unsigned long long)(words * 8));
-  }
-  uint64_t *d_res = (uint64_t *)(B.d_tree + P.tree_bytes);
+  uint64_t *d_res = (uint64_t *)(d_tree + P.tree_bytes);
 
   uint64_t listed = 0;
   auto add = [&](uint32_t reason, uint32_t level, uint64_t block, uint64_t lo, uint64_t hi, uint64_t off) {
@@ -598,16 +516,16 @@ int verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t 
   auto harvest_tree = [&]() {
     if (tree_seen) return;
     tree_seen = true;
-    rep->bad_hash = B.h_res[0];
-    rep->bad_spare = (uint64_t)__builtin_popcountll(B.h_res[1]);
+    rep->bad_hash = h_res[0];
+    rep->bad_spare = (uint64_t)__builtin_popcountll(h_res[1]);
     for (uint32_t l = P.levels; l-- > 0;) {
       if (rep->bad_hash && listed < bad_cap)
-        each_set_bit(B.h_res + 2, P.first[l], P.first[l] + P.blocks[l], [&](uint64_t t) {
+        each_set_bit(h_res + 2, P.first[l], P.first[l] + P.blocks[l], [&](uint64_t t) {
           const VerityBlockLoc b = verity_locate(G, t);
           return add(NGPU_VERITY_BAD_HASH, b.level, t, b.first_data, b.last_data,
                      hash_offset + t * kVerityHashBlock);
         });
-      if (B.h_res[1] >> l & 1) {
+      if (h_res[1] >> l & 1) {
         const uint64_t t = P.first[l] + P.blocks[l] - 1;
         const VerityBlockLoc b = verity_locate(G, t);
         add(NGPU_VERITY_BAD_SPARE, l, t, b.first_data, b.last_data, hash_offset + t * kVerityHashBlock);
@@ -622,7 +540,7 @@ int verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t 
   auto harvest = [&](int k) {
     if (!held[k].n) return;
     harvest_tree();  // enqueued before any window: it has landed too
-    const uint64_t *r = B.h_res + at[k];
+    const uint64_t *r = h_res + at[k];
     rep->bad_data += r[0];
     if (r[0] && listed < bad_cap)  // the bitmap is scanned only when the count says so
       each_set_bit(r + 1, 0, held[k].n, [&](uint64_t i) {
@@ -651,15 +569,15 @@ int verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t 
     const uint64_t off = j * win, n = std::min(win, P.tree_bytes - off);
     int k;
     if (int rc = fill(hash_offset + off, n, &k)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(B.d_tree + off, B.win[k].h, n, hipMemcpyHostToDevice, B.s));
+    HIP_TRY(e, hipMemcpyAsync(d_tree + off, B.win[k].h, n, hipMemcpyHostToDevice, B.s));
     HIP_TRY(e, hipEventRecord(B.done[k], B.s));
   }
   {
     std::lock_guard<std::mutex> g(e->mu);
-    if (int rc = enqueue_verify_tree(e, P, B.d_tree, root, d_res + 2, d_res, B.s)) return rc;
+    if (int rc = enqueue_verify_tree(e, P, d_tree, root, d_res + 2, d_res, B.s)) return rc;
   }
   HIP_TRY(e, hipEventRecord(B.fence, B.s));  // system-scope release before the host's copy
-  HIP_TRY(e, hipMemcpyAsync(B.h_res, d_res, (2 + tw) * 8, hipMemcpyDeviceToHost, B.s));
+  HIP_TRY(e, hipMemcpyAsync(h_res, d_res, (2 + tw) * 8, hipMemcpyDeviceToHost, B.s));
 
   // ---- the image, window by window, against the tree in HBM ----------------
   for (uint64_t wi = 0; wi < nwin; ++wi) {
@@ -670,13 +588,10 @@ int verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t 
     {
       std::lock_guard<std::mutex> g(e->mu);
       if (int rc = enqueue_verify_data(e, P, (const uint8_t *)B.win[k].d, off / kVerityDataBlock, nb,
-                                       B.d_tree, root, d_res + at[k] + 1, d_res + at[k], B.s))
+                                       d_tree, root, d_res + at[k] + 1, d_res + at[k], B.s))
         return rc;
     }
-    HIP_TRY(e, hipEventRecord(B.fence, B.s));
-    HIP_TRY(e, hipMemcpyAsync(B.h_res + at[k], d_res + at[k], (1 + (nb + 63) / 64) * 8,
-                              hipMemcpyDeviceToHost, B.s));
-    HIP_TRY(e, hipEventRecord(B.done[k], B.s));
+    if (int rc = B.verdict_back(k, h_res + at[k], d_res + at[k], (1 + (nb + 63) / 64) * 8)) return rc;
     held[k].block0 = off / kVerityDataBlock;
     held[k].n = nb;
   }
@@ -734,9 +649,8 @@ int ngpu_verity_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint64_t da
                       const ngpu_verity_options *opt, ngpu_write_fn w, void *wctx,
                       ngpu_verity_info *info) {
   if (!e || !ra || !info) return NGPU_EINVAL;
-  const int rc = guarded([&]() -> int { return verity_image(e, ra, ctx, data_bytes, opt, w, wctx, info); });
-  if (rc == NGPU_ENOMEM) fail(e, rc, "verity: out of memory");
-  return rc;
+  return guarded_entry(e, "verity",
+                       [&]() -> int { return verity_image(e, ra, ctx, data_bytes, opt, w, wctx, info); });
 }
 
 int ngpu_verity_verify_tree_device(ngpu_engine *e, uint64_t data_bytes, const void *d_tree,
@@ -781,11 +695,9 @@ int ngpu_verity_verify_image(ngpu_engine *e, ngpu_read_at_fn ra, void *ctx, uint
                              uint64_t hash_offset, const uint8_t root[32], const ngpu_verity_options *opt,
                              ngpu_verity_report *report, ngpu_verity_bad *bad, uint64_t bad_cap) {
   if (!e || !ra || !root || !report || (bad_cap && !bad)) return NGPU_EINVAL;
-  const int rc = guarded([&]() -> int {
+  return guarded_entry(e, "verity", [&]() -> int {
     return verity_verify_image(e, ra, ctx, data_bytes, hash_offset, root, opt, report, bad, bad_cap);
   });
-  if (rc == NGPU_ENOMEM) fail(e, rc, "verity: out of memory");
-  return rc;
 }
 
 }  // extern "C"
