@@ -220,8 +220,9 @@ int ngpu_free_pinned(ngpu_engine *eng, void *ptr);
 /* ---- chunk dict handles (PackOption.ChunkDictPath; builder.go:122-124) ----
  * The reference runs one nydus-image process per Pack, each loading its own
  * `--chunk-dict bootstrap=P` ([nydus v2.3.0] HashChunkDict).  Here a dict is
- * an HBM-resident, read-only, reference-counted object: a Pack captures the
- * dict it is opened with, so packs with different dicts (or none) can be open
+ * an HBM-resident, reference-counted object, immutable per handle
+ * (ngpu_dict_extend returns a new one and leaves its base as it was): a Pack
+ * captures the dict it is opened with, so packs with different dicts (or none) can be open
  * on one engine at once, and 1000 Packs against one ChunkDictPath share one
  * loaded table.  First table entry wins for duplicate digests; usize == 0
  * matches any chunk size.
@@ -260,6 +261,48 @@ int ngpu_dict_create_device_gid(ngpu_engine *eng, const uint8_t *d_digests,
                                 const uint32_t *d_chunk_index, const uint64_t *d_uoff,
                                 const uint32_t *d_gid, uint64_t n, uint32_t n_blobs,
                                 ngpu_dict **out);
+/* ---- dict extend: fold a converted layer's records into a dict ----
+ * out = base followed by n more 80-B RAFS v6 chunk-info records.  Equal, for every
+ * probe, Pack, Check and stats field, to ngpu_dict_create over
+ *   records(base) ++ records with blob_index += blobs(base),  blob_table(base) ++ blob_table.
+ * First table entry still wins: a digest base already holds keeps base's row.
+ * base is not modified and not released; out carries one reference.  flags must be 0.
+ *
+ * When base is the newest handle on its storage and the storage has room, the
+ * records are appended in place (n record writes, n table inserts; no copy,
+ * no rebuild: the cost does not depend on base's size) and out shares base's
+ * HBM; otherwise out gets a storage half as large again, base's records are
+ * copied device to device and the table is built over all of them.  A dict from
+ * ngpu_dict_open / ngpu_dict_create* is allocated exactly, so its first extend
+ * copies.  Handles of one storage free it when the last of them is released.
+ * Safe against probes of base (and of any older handle) running on other
+ * streams and threads meanwhile; two threads extending one base at once get
+ * one in-place result and one copy.  The device work runs on a stream of the
+ * library's own and is complete when the call returns.
+ *
+ * Rejected before any GPU work: base == NULL, flags != 0 or n && !records
+ * (NGPU_EINVAL); entries(base) + n >= 0xFFFFFFFF or more than 2^20 blobs (as
+ * ngpu_dict_create); a record whose blob_index >= n_blobs when a table is given
+ * (NGPU_EFORMAT); a node dict (NGPU_EINVAL: ngpu_node_dict_extend).  Blob table:
+ * out has one iff base has one and the call passes one; when neither does, out
+ * has only a blob count; exactly one side with a table is NGPU_EINVAL (nothing
+ * is dropped silently).  A base of 0 blobs goes with either, and so does a call
+ * with n == 0 and no table, which returns a handle equal to base.  out keeps
+ * compressed placements (what a Pack's DICT records copy) iff base did or base
+ * was empty.  On failure *out is NULL and base is untouched. */
+int ngpu_dict_extend(ngpu_engine *eng, ngpu_dict *base, const void *records, uint64_t n,
+                     const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
+/* The same from a RAFS v6 bootstrap file (its chunk table and blob table), with
+ * ngpu_dict_open's compatibility checks (digester flag, chunk size, FsVersion 6). */
+int ngpu_dict_extend_bootstrap(ngpu_engine *eng, ngpu_dict *base, const char *path,
+                               uint32_t flags, ngpu_dict **out);
+typedef struct {
+  uint64_t entries, blobs;
+  uint64_t record_capacity, table_capacity; /* of the storage it sits on (node dict: part 0) */
+  uint32_t shares_base_storage;             /* 1: made by an in-place extend */
+  uint32_t reserved[3];
+} ngpu_dict_info;
+int ngpu_dict_info_get(const ngpu_dict *d, ngpu_dict_info *out);
 void ngpu_dict_retain(ngpu_dict *d);
 void ngpu_dict_release(ngpu_dict *d);
 uint64_t ngpu_dict_entries(const ngpu_dict *d);
@@ -522,6 +565,12 @@ ngpu_engine *ngpu_node_engine(ngpu_node *node, uint32_t i);
  * the same mode again returns the same dict with one more reference, so 1000
  * Packs naming one ChunkDictPath load it once per node. */
 int ngpu_node_dict_open(ngpu_node *node, const char *path, uint32_t mode, ngpu_dict **out);
+/* ngpu_dict_extend for node dicts: a partitioned dict gives each part the
+ * records it owns (global ids entries(base) + position), a replicated one gives
+ * every replica all of them; the exchange mode is base's.  Each part appends
+ * in place or copies by its own fill.  A plain dict here is NGPU_EINVAL. */
+int ngpu_node_dict_extend(ngpu_node *node, ngpu_dict *base, const void *records, uint64_t n,
+                          const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
 int ngpu_node_dict_create(ngpu_node *node, const void *records, uint64_t n,
                           const void *blob_table, uint32_t n_blobs, uint32_t mode,
                           ngpu_dict **out);

@@ -231,6 +231,8 @@ struct alignas(64) DictRec {
 };
 static_assert(sizeof(DictRec) == 64, "DictRec is 64 bytes");
 
+// rec / table / mask are the storage's (engine_internal.hpp DictStorage), m is
+// the handle's: slots whose id is >= m belong to later handles and are skipped.
 struct DictDevice {
   const DictRec *rec = nullptr;      // m records, table order
   const uint64_t *table = nullptr;   // hash slots {tag : local id}
@@ -242,6 +244,10 @@ struct DictDevice {
 // dedup.hip
 void launch_dict_build(const DictRec *rec, uint64_t m, uint64_t *table, uint64_t cap,
                        hipStream_t s);
+// Insert entries [first, m) into a live table (in-place dict extend): their
+// records must have been written by an earlier launch on s.
+void launch_dict_insert_range(const DictRec *rec, uint64_t first, uint64_t m, uint64_t *table,
+                              uint64_t cap, hipStream_t s);
 // hits == nullptr: probe `dict`; otherwise use the given per-chunk hits.
 // n_blobs: inner blobs of the (global) dict.  L layers; layer l owns chunks
 // [lfirst[l], lfirst[l+1]) (device array; nullptr = one layer, {0, n} is
@@ -289,9 +295,9 @@ void launch_remark_digested(ngpu_result *res, uint64_t n, hipStream_t s);
 void launch_hits_scatter(const ngpu_dict_hit *routed, const uint32_t *rows, uint64_t m,
                          ngpu_dict_hit *hits, hipStream_t s);
 // RAFS v6 chunk records (80 B, device) -> dict records; gid = gids[i] (device
-// array) or gid0 + i.
+// array) or gid0 + i; blob0 is added to every record's blob index.
 void launch_dict_unpack(const uint8_t *recs, uint64_t n, const uint32_t *gids, uint32_t gid0,
-                        DictRec *out, hipStream_t s);
+                        DictRec *out, hipStream_t s, uint32_t blob0 = 0);
 // Device SoA arrays -> dict records (index / uoff may be null: 0), gid =
 // gid[i] (null: i).
 void launch_dict_pack(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,

@@ -91,9 +91,14 @@ __device__ uint32_t ht_lookup(const uint64_t *table, uint64_t mask,
   }
 }
 
-__global__ void dict_insert(const DictRec *__restrict__ rec, uint64_t m,
+// Entries [first, m) into the table.  A build inserts [0, m) into a cleared
+// table; an in-place dict extend inserts its new ids into the live one, after
+// the launch that wrote their records (the duplicate check below reads other
+// new records' digests: fused with the unpack, a neighbour's record might not
+// be written yet, and two slots would end up holding one digest).
+__global__ void dict_insert(const DictRec *__restrict__ rec, uint64_t first, uint64_t m,
                             uint64_t *__restrict__ table, uint64_t mask) {
-  const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t e = first + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (e < m)
     ht_insert_min<sizeof(DictRec)>(table, mask, reinterpret_cast<const uint8_t *>(rec), (uint32_t)e);
 }
@@ -119,6 +124,9 @@ __device__ __forceinline__ ngpu_dict_hit dict_hit_of(const DictDevice &dict, uin
 // line had often left the L2 (random lines turn the L2 over in a few us) and
 // the re-read went to HBM: +0.35 line per probe at 30 % hits (1.94 -> 1.60;
 // dict_probe_variant RV 2..4 took the probe apart, tools/probe_sweep.py).
+// Slots whose id is >= dict.m are skipped unread: that is what keeps a handle
+// blind to in-place appends behind it (dict.hip "dict extend"; for a node shard
+// dict.m is the part's local count, as table ids are local).
 __device__ __forceinline__ ngpu_dict_hit dict_find(const DictDevice &dict, const uint32_t d[8]) {
   const uint32_t tag = digest_tag(d);
   for (uint64_t p = digest_bucket(d) & dict.mask;; p = (p + 1) & dict.mask) {
@@ -126,6 +134,9 @@ __device__ __forceinline__ ngpu_dict_hit dict_find(const DictDevice &dict, const
     if (s == kEmpty) break;
     if ((uint32_t)(s >> 32) != tag) continue;
     const uint32_t e = (uint32_t)s;
+    // an entry a later handle appended to the storage this dict shares (dict
+    // extend): not this handle's, and its record may not be written yet
+    if (e >= dict.m) continue;
     const uint4 *r = reinterpret_cast<const uint4 *>(dict.rec + e);
     const uint4 a = r[0], b = r[1], f = r[2];
     const uint64_t uo = dict.rec[e].uoff;
@@ -179,7 +190,9 @@ __global__ __launch_bounds__(256) void dict_probe_records(const uint8_t *__restr
 // dict_probe_variant, dict_probe_coop; DESIGN.md §3 "dict probe") are built
 // only with -DNGPU_PROBE_AB=1 (scripts/build_ab.sh), never into the product
 // library; their launch knobs (NGPU_PROBE_VARIANT / NGPU_PROBE_COOP) exist
-// only in such a build.
+// only in such a build.  They do not carry dict_find's `id >= dict.m` skip, so
+// an A/B build must not probe a handle that an in-place dict extend has grown
+// past (ngpu_dict_extend); the tools that use them build their dicts in one go.
 #ifndef NGPU_PROBE_AB
 #define NGPU_PROBE_AB 0
 #endif
@@ -481,7 +494,7 @@ __global__ __launch_bounds__(256) void dict_probe_coop(const uint8_t *__restrict
 // compressed_size, uncompressed_size, compressed_offset, uncompressed_offset,
 // file_offset, index, reserved) -> dict records.  One thread per record.
 __global__ void dict_unpack(const uint8_t *__restrict__ recs, uint64_t n,
-                            const uint32_t *__restrict__ gids, uint32_t gid0,
+                            const uint32_t *__restrict__ gids, uint32_t gid0, uint32_t blob0,
                             DictRec *__restrict__ out) {
   const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -490,7 +503,7 @@ __global__ void dict_unpack(const uint8_t *__restrict__ recs, uint64_t n,
   uint4 *o = reinterpret_cast<uint4 *>(out + i);
   o[0] = a;
   o[1] = b;
-  o[2] = make_uint4(c.w, c.x, f.z, gids ? gids[i] : gid0 + (uint32_t)i);
+  o[2] = make_uint4(c.w, c.x + blob0, f.z, gids ? gids[i] : gid0 + (uint32_t)i);
   o[3] = make_uint4(d.z, d.w, 0, 0);
 }
 
@@ -1345,7 +1358,16 @@ void launch_dict_build(const DictRec *rec, uint64_t m, uint64_t *table, uint64_t
   hipMemsetAsync(table, 0xFF, cap * sizeof(uint64_t), s);
   if (m == 0) return;
   const uint64_t blocks = (m + 255) / 256;
-  hipLaunchKernelGGL(dict_insert, dim3((unsigned)blocks), dim3(256), 0, s, rec, m, table, cap - 1);
+  hipLaunchKernelGGL(dict_insert, dim3((unsigned)blocks), dim3(256), 0, s, rec, (uint64_t)0, m, table,
+                     cap - 1);
+}
+
+void launch_dict_insert_range(const DictRec *rec, uint64_t first, uint64_t m, uint64_t *table,
+                              uint64_t cap, hipStream_t s) {
+  if (first >= m) return;
+  const uint64_t blocks = (m - first + 255) / 256;
+  hipLaunchKernelGGL(dict_insert, dim3((unsigned)blocks), dim3(256), 0, s, rec, first, m, table,
+                     cap - 1);
 }
 
 void launch_dict_probe(const uint8_t *digests, uint64_t stride, uint64_t n,
@@ -1619,10 +1641,10 @@ void launch_hits_merge(const uint8_t *q, uint64_t n, uint32_t W, const ngpu_dict
 }
 
 void launch_dict_unpack(const uint8_t *recs, uint64_t n, const uint32_t *gids, uint32_t gid0,
-                        DictRec *out, hipStream_t s) {
+                        DictRec *out, hipStream_t s, uint32_t blob0) {
   if (n == 0) return;
   hipLaunchKernelGGL(dict_unpack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, recs, n, gids,
-                     gid0, out);
+                     gid0, blob0, out);
 }
 
 void launch_dict_pack(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,

@@ -8,14 +8,17 @@
 // and a Pack pins the dict it was opened with, so packs against different
 // dicts can be open on one engine at once.
 //
-// Layout in HBM per dict of m entries (table order): digests u8[m][32],
-// usize / blob / index u32[m], uoff u64[m], hash slots u64[next_pow2(2m+16)]
-// (open addressing, dedup.hip).  The compressed placement a layer's DICT
-// records copy (offset, size, flags) stays on the host: only the blob writer
-// reads it.
+// Layout in HBM per dict of m entries (table order): 64-B records (digest,
+// usize, blob, index, global id, uoff), hash slots u64[next_pow2(2m+16)] (open
+// addressing, dedup.hip).  The compressed placement a layer's DICT records copy
+// (offset, size, flags) stays on the host: only the blob writer reads it.
+// Records, table and placement rows belong to a reference-counted DictStorage;
+// a handle is immutable, and ngpu_dict_extend ("dict extend" below) puts a new
+// handle on the same storage when there is room, else on a larger one.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -26,6 +29,7 @@
 #include <thread>
 
 #include "blob.hpp"
+#include "dict_grow_plan.hpp"
 #include "engine_internal.hpp"
 
 using namespace ngpu;
@@ -40,12 +44,22 @@ void dict_ref(ngpu_dict *d) {
   if (d) d->refs.fetch_add(1, std::memory_order_relaxed);
 }
 
+// The last handle on a storage frees it: handles of one storage share its
+// records and table, so nothing is freed while any of them can still be probed.
+void storage_unref(DictStorage *st) {
+  if (!st || st->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  DeviceGuard g(st->device);
+  // hipFree waits for the device, so no queued probe still reads the table
+  if (st->rec) (void)hipFree(st->rec);
+  if (st->table) (void)hipFree(st->table);
+  free(st->place);
+  delete st;
+}
+
 void dict_unref(ngpu_dict *d) {
   if (!d || d->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
   if (!d->req.empty() || !d->parts.empty()) node_dict_free(d);
-  DeviceGuard g(d->device);
-  // hipFree waits for the device, so no queued probe still reads the table
-  for (void *p : d->allocs) (void)hipFree(p);
+  storage_unref(d->st);
   delete d;
 }
 
@@ -69,25 +83,54 @@ ngpu_dict *default_dict(ngpu_engine *e) {  // e->mu held
   return e->dict;
 }
 
-// Allocate the records and hash table of an m-entry dict.
-int dict_alloc(ngpu_engine *e, ngpu_dict *d, uint64_t m, uint32_t n_blobs) {
-  const uint64_t cap = next_pow2(2 * m + 16);
+// A storage of rec_cap record slots and table_cap hash slots (place: with host
+// placement rows), none of them reserved yet.  The rows are malloc'ed, not
+// zeroed: the pages past the last row written are never touched.
+static int storage_alloc(ngpu_engine *e, uint64_t rec_cap, uint64_t table_cap, bool place,
+                         DictStorage **out) {
+  DictStorage *st = new DictStorage();
+  st->device = e->device;
+  st->rec_cap = rec_cap;
+  st->table_cap = table_cap;
+  const uint64_t bytes[2] = {rec_cap * sizeof(DictRec), table_cap * 8};
   void *p[2] = {};
-  const uint64_t bytes[2] = {m * sizeof(DictRec), cap * 8};
   for (int i = 0; i < 2; ++i) {
     if (hipMalloc(&p[i], bytes[i] ? bytes[i] : 64) != hipSuccess) {
-      (void)hipGetLastError();  // the caller's dict_unref frees p[0..i)
+      (void)hipGetLastError();
+      if (p[0]) (void)hipFree(p[0]);
+      delete st;
       return fail(e, NGPU_ENOMEM, "chunk dict: %llu entries do not fit in HBM",
-                  (unsigned long long)m);
+                  (unsigned long long)rec_cap);
     }
-    d->allocs.push_back(p[i]);
   }
+  st->rec = (DictRec *)p[0];
+  st->table = (uint64_t *)p[1];
+  if (place && rec_cap && !(st->place = (DictPlace *)malloc(rec_cap * sizeof(DictPlace)))) {
+    storage_unref(st);
+    return fail(e, NGPU_ENOMEM, "chunk dict: no host memory for %llu placement rows",
+                (unsigned long long)rec_cap);
+  }
+  *out = st;
+  return 0;
+}
+
+// Point d at entries [0, m) of the storage it holds.
+static void dict_bind(ngpu_dict *d, uint64_t m, uint32_t n_blobs) {
   DictDevice &v = d->dev;
-  v.rec = (const DictRec *)p[0];
-  v.table = (const uint64_t *)p[1];
-  v.mask = cap - 1;
+  v.rec = d->st->rec;
+  v.table = d->st->table;
+  v.mask = d->st->table_cap - 1;
   v.m = m;
   v.n_blobs = n_blobs;
+}
+
+// Allocate the records and hash table of an m-entry dict: a storage of its
+// own, exactly its size and all of it reserved.
+int dict_alloc(ngpu_engine *e, ngpu_dict *d, uint64_t m, uint32_t n_blobs, bool place) {
+  if (int rc = storage_alloc(e, m, next_pow2(2 * m + 16), place, &d->st)) return rc;
+  d->st->used = m;
+  d->has_place = place && m;
+  dict_bind(d, m, n_blobs);
   return 0;
 }
 
@@ -151,15 +194,14 @@ int dict_from_records(ngpu_engine *e, const uint8_t *recs, uint64_t m, const uin
   }
   if (nb > (1u << 20)) return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", nb - 1);
   ngpu_dict *d = dict_new(e);
-  int rc = dict_alloc(e, d, m, nb);
+  int rc = dict_alloc(e, d, m, nb, true);
   if (rc) {
     dict_unref(d);
     return rc;
   }
-  d->place.resize(m);
   for (uint64_t i = 0; i < m; ++i) {
     const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-    d->place[i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+    d->st->place[i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
   }
   if (blobs && n_blobs) d->blob_table.assign(blobs, blobs + 256ull * n_blobs);
   // upload in batches of <= 1M records, unpack to dict records on the GPU
@@ -209,7 +251,7 @@ int dict_from_arrays(ngpu_engine *e, const uint8_t *dg, const uint32_t *us, cons
   if (n_blobs > (1u << 20)) return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large",
                                         n_blobs - 1);
   ngpu_dict *d = dict_new(e);
-  int rc = dict_alloc(e, d, m, n_blobs);
+  int rc = dict_alloc(e, d, m, n_blobs, false);
   if (rc) {
     dict_unref(d);
     return rc;
@@ -240,6 +282,217 @@ int dict_from_arrays(ngpu_engine *e, const uint8_t *dg, const uint32_t *us, cons
     return rc;
   }
   *out = d;
+  return 0;
+}
+
+// ---- dict extend ---------------------------------------------------------------
+// A handle never changes; ngpu_dict_extend returns a new one that answers as a
+// dict created from the concatenation would.  When the base is the newest
+// handle on its storage and the storage has room (dict_grow_plan.hpp) the k
+// records are appended in place: the unpack kernel writes rec[m, m + k), then a
+// second launch inserts ids m .. m + k - 1 into the live table.  Older handles
+// (and kernels probing them on other streams meanwhile) do not see any of it:
+// new entries take only slots that were empty, never displace an entry and
+// never win an atomicMin against a smaller id, so an old handle's chain still
+// ends where it ended or walks over new slots, which dict_find skips unread
+// because their id is >= the handle's m.  Otherwise the result goes onto a new
+// storage half as large again: base's records copied device to device, the new
+// ones unpacked behind them, the table built over all of them.
+
+int dict_extend_check(ngpu_engine *e, const ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                      const uint8_t *blobs, uint32_t n_blobs, uint32_t *nb_out, bool *with_table) {
+  const uint64_t m = base->dev.m;
+  if (m >= kDictMaxEntries || k >= kDictMaxEntries - m)
+    return fail(e, NGPU_EINVAL, "chunk dict too large (%llu entries)", (unsigned long long)(m + k));
+  uint32_t nb = 0;
+  for (uint64_t i = 0; i < k; ++i) {
+    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
+    if (n_blobs && r->blob_index >= n_blobs)
+      return fail(e, NGPU_EFORMAT, "chunk dict record points at blob %u of %u", r->blob_index,
+                  n_blobs);
+    if (r->blob_index >= (1u << 20))
+      return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", r->blob_index);
+    nb = std::max(nb, r->blob_index + 1);
+  }
+  if (n_blobs) nb = n_blobs;
+  if (nb > (1u << 20) || base->dev.n_blobs + nb > (1u << 20))
+    return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", base->dev.n_blobs + nb - 1);
+  // the blob table: kept only when both sides have one; a base of 0 blobs goes
+  // with either, and so does a call that adds nothing
+  const bool base_has = !base->blob_table.empty(), call_has = blobs && n_blobs;
+  if (base->dev.n_blobs == 0 && !base_has) {
+    *with_table = call_has;
+  } else if (k == 0 && n_blobs == 0) {
+    *with_table = base_has;
+  } else if (base_has != call_has) {
+    return fail(e, NGPU_EINVAL,
+                base_has ? "dict extend: the base has a blob table, the new records come without one"
+                         : "dict extend: the base has no blob table, the new records come with one");
+  } else {
+    *with_table = base_has;
+  }
+  *nb_out = base->dev.n_blobs + nb;
+  return 0;
+}
+
+int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                        uint32_t blob0, uint32_t nb, const uint32_t *gids, bool place,
+                        ngpu_dict **out) {
+  DeviceGuard dg(e->device);
+  DictStorage *st = base->st;
+  const uint64_t m = base->dev.m;
+  const bool want_place = place && (base->has_place || m == 0);
+  DictGrowPlan plan;
+  bool share = k == 0;  // nothing to write: another handle on the same entries
+  if (k) {
+    std::lock_guard<std::mutex> g(st->mu);
+    plan = dict_grow_plan(m, st->used, st->rec_cap, st->table_cap, k);
+    if (!plan.ok)
+      return fail(e, NGPU_EINVAL, "chunk dict too large (%llu entries)", (unsigned long long)(m + k));
+    if (plan.share && want_place && !st->place)  // (an empty handle on a storage without rows)
+      plan = dict_grow_plan(m, m + 1, st->rec_cap, st->table_cap, k);
+    share = plan.share;
+    // the id range [m, m + k) is this call's from here on; if the call fails it
+    // stays dead: no handle reaches it and nobody appends to this storage again
+    if (share) st->used = m + k;
+  }
+  DictStorage *dst = st;
+  if (!share) {
+    if (int rc = storage_alloc(e, plan.rec_cap, plan.table_cap, want_place, &dst)) return rc;
+    dst->used = m + k;
+  } else {
+    st->refs.fetch_add(1, std::memory_order_relaxed);
+  }
+  int rc = 0;
+  if (k) {
+    BuildStream bs(e->device);
+    const uint64_t batch = std::min<uint64_t>(k, 1u << 20);
+    uint8_t *tmp = nullptr;
+    uint32_t *tmp_gid = nullptr;
+    if (!bs.s) {
+      rc = fail(e, NGPU_EHIP, "chunk dict: no build stream");
+    } else if (hipMalloc((void **)&tmp, batch * 80) != hipSuccess ||
+               (gids && hipMalloc((void **)&tmp_gid, batch * 4) != hipSuccess)) {
+      (void)hipGetLastError();
+      rc = fail(e, NGPU_ENOMEM, "chunk dict: staging allocation failed");
+    }
+    // NGPU_DICT_TRACE=1: one stderr line per extend with its device time -- an
+    // in-place append from before its first launch (after the records' upload)
+    // to the end of the inserts, a copy from before the device-to-device copy to
+    // the end of the table build (tools/dict_extend_bench.py reads it); off: no
+    // event is made
+    static const bool trace = [] {
+      const char *v = getenv("NGPU_DICT_TRACE");
+      return v && v[0] == '1';
+    }();
+    hipEvent_t tev[2] = {};
+    if (!rc && trace)
+      for (hipEvent_t &x : tev)
+        if (hipEventCreate(&x) != hipSuccess) x = nullptr;
+    if (!share && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs.s);
+    if (!rc && !share && m &&
+        hipMemcpyAsync(dst->rec, st->rec, m * sizeof(DictRec), hipMemcpyDeviceToDevice, bs.s) !=
+            hipSuccess)
+      rc = fail(e, NGPU_EHIP, "chunk dict: copy of the base's records failed");
+    if (!rc && want_place) {
+      if (!share && base->has_place) memcpy(dst->place, st->place, m * sizeof(DictPlace));
+      for (uint64_t i = 0; i < k; ++i) {
+        const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
+        dst->place[m + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+      }
+    }
+    // launch 1 (per batch of <= 1M records): rec[m + a ..) from the 80-B records
+    for (uint64_t a = 0; a < k && !rc; a += batch) {
+      const uint64_t c = std::min(batch, k - a);
+      if (hipMemcpyAsync(tmp, recs + 80 * a, c * 80, hipMemcpyHostToDevice, bs.s) != hipSuccess ||
+          (gids && hipMemcpyAsync(tmp_gid, gids + a, c * 4, hipMemcpyHostToDevice, bs.s) !=
+                       hipSuccess)) {
+        rc = fail(e, NGPU_EHIP, "chunk dict: upload failed");
+        break;
+      }
+      if (share && a == 0 && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs.s);
+      launch_dict_unpack(tmp, c, gids ? tmp_gid : nullptr, (uint32_t)(m + a), dst->rec + m + a, bs.s,
+                         blob0);
+      // the next batch overwrites tmp (one batch: the sync after the inserts serves)
+      if (a + c < k && hipStreamSynchronize(bs.s) != hipSuccess)
+        rc = fail(e, NGPU_EHIP, "chunk dict: unpack failed");
+    }
+    // launch 2, after every record is written: the new ids into the live table
+    // (share), or the whole table of the new storage (fork)
+    if (!rc) {
+      if (share)
+        launch_dict_insert_range(dst->rec, m, m + k, dst->table, dst->table_cap, bs.s);
+      else
+        launch_dict_build(dst->rec, m + k, dst->table, dst->table_cap, bs.s);
+      if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: table insert failed");
+    }
+    if (tev[0] && tev[1]) (void)hipEventRecord(tev[1], bs.s);
+    if (bs.s && hipStreamSynchronize(bs.s) != hipSuccess && !rc)
+      rc = fail(e, NGPU_EHIP, "chunk dict: extend failed");
+    if (tev[0] && tev[1]) {
+      float ms = 0;
+      if (!rc && hipEventElapsedTime(&ms, tev[0], tev[1]) == hipSuccess)
+        fprintf(stderr, "ngpu dict_extend %s m=%llu k=%llu device_us=%.1f\n", share ? "share" : "fork",
+                (unsigned long long)m, (unsigned long long)k, ms * 1000.0);
+    }
+    for (hipEvent_t x : tev)
+      if (x) (void)hipEventDestroy(x);
+    if (tmp_gid) (void)hipFree(tmp_gid);
+    if (tmp) (void)hipFree(tmp);
+  }
+  if (rc) {
+    storage_unref(dst);
+    return rc;
+  }
+  ngpu_dict *d = new ngpu_dict();
+  d->device = base->device;
+  d->digester = base->digester;
+  d->chunk_size = base->chunk_size;
+  d->st = dst;
+  d->has_place = want_place && m + k;
+  d->shares_base = share;
+  dict_bind(d, m + k, nb);
+  *out = d;
+  return 0;
+}
+
+int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                      ngpu_dict *out) {
+  const uint64_t m = base ? base->dev.m : 0;
+  DictStorage *st = base ? base->st : nullptr;
+  const bool base_rows = base && base->has_place && st && st->place;
+  if (m && !base_rows) return 0;  // base keeps no rows: neither does the result
+  bool share = false;
+  DictGrowPlan plan;
+  if (st) {
+    std::lock_guard<std::mutex> g(st->mu);
+    plan = dict_grow_plan(m, st->used, st->rec_cap, ~0ull, k);
+    share = plan.ok && plan.share && (st->place || k == 0);
+    if (share && k) st->used = m + k;
+  }
+  if (share) {
+    st->refs.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    // creation (no base): exactly k rows; a fork: half as many again
+    const uint64_t cap = st ? dict_grow_plan(m, m + 1, 0, 0, k).rec_cap : k;
+    st = new DictStorage();
+    st->device = e->device;
+    st->rec_cap = cap;
+    st->table_cap = ~0ull;
+    st->used = m + k;
+    if (cap && !(st->place = (DictPlace *)malloc(cap * sizeof(DictPlace)))) {
+      delete st;
+      return fail(e, NGPU_ENOMEM, "chunk dict: no host memory for %llu placement rows",
+                  (unsigned long long)cap);
+    }
+    if (base_rows) memcpy(st->place, base->st->place, m * sizeof(DictPlace));
+  }
+  for (uint64_t i = 0; i < k; ++i) {
+    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
+    st->place[m + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+  }
+  out->st = st;
+  out->has_place = m + k != 0;
   return 0;
 }
 
@@ -389,7 +642,7 @@ int dict_stream_v6(ngpu_engine *e, const char *path, uint64_t cto, uint64_t m,
   ngpu_dict *d = dict_new(e);
   uint8_t *pin[3] = {}, *tmp[2] = {};
   hipEvent_t ev[3] = {};
-  int rc = dict_alloc(e, d, m, n_blobs);
+  int rc = dict_alloc(e, d, m, n_blobs, true);
   for (int i = 0; i < 3 && !rc; ++i)
     if (hipHostMalloc((void **)&pin[i], kStreamPiece * 80, hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess)
@@ -397,7 +650,6 @@ int dict_stream_v6(ngpu_engine *e, const char *path, uint64_t cto, uint64_t m,
   for (int i = 0; i < 2 && !rc; ++i)
     if (hipMalloc((void **)&tmp[i], kStreamPiece * 80) != hipSuccess)
       rc = fail(e, NGPU_ENOMEM, "chunk dict: staging allocation failed");
-  if (!rc) d->place.resize(m);
   if (!rc && n_blobs) d->blob_table.assign(blobs.begin(), blobs.end());
   DictRec *rec = const_cast<DictRec *>(d->dev.rec);
   uint32_t nb = 0;
@@ -425,7 +677,7 @@ int dict_stream_v6(ngpu_engine *e, const char *path, uint64_t cto, uint64_t m,
         for (uint64_t i = r0; i < r1; ++i) {
           const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(h + 80 * i);
           x = std::max(x, r->blob_index + 1);
-          d->place[a + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+          d->st->place[a + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
         }
         tnb[t] = x;
       });
@@ -588,6 +840,70 @@ int ngpu_dict_create(ngpu_engine *e, const void *records, uint64_t n, const void
     return dict_from_records(e, (const uint8_t *)records, n, (const uint8_t *)blob_table, n_blobs,
                              out, nullptr);
   });
+}
+
+static int dict_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t n,
+                       const uint8_t *blobs, uint32_t n_blobs, ngpu_dict **out) {
+  if (!base->parts.empty())
+    return fail(e, NGPU_EINVAL, "dict extend: a node dict is extended with ngpu_node_dict_extend");
+  if (base->device != e->device)
+    return fail(e, NGPU_EINVAL, "chunk dict lives on device %d, engine on %d", base->device,
+                e->device);
+  if (int rc = dict_check(e, base)) return rc;
+  uint32_t nb = 0;
+  bool with_table = false;
+  if (int rc = dict_extend_check(e, base, recs, n, blobs, n_blobs, &nb, &with_table)) return rc;
+  ngpu_dict *d = nullptr;
+  if (int rc = dict_extend_records(e, base, recs, n, base->dev.n_blobs, nb, nullptr, true, &d))
+    return rc;
+  if (with_table) {
+    d->blob_table = base->blob_table;
+    if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
+  }
+  *out = d;
+  return 0;
+}
+
+int ngpu_dict_extend(ngpu_engine *e, ngpu_dict *base, const void *records, uint64_t n,
+                     const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !e || !out || (n && !records) || (n_blobs && !blob_table))
+    return NGPU_EINVAL;
+  return guarded([&] {
+    return dict_extend(e, base, (const uint8_t *)records, n, (const uint8_t *)blob_table, n_blobs,
+                       out);
+  });
+}
+
+int ngpu_dict_extend_bootstrap(ngpu_engine *e, ngpu_dict *base, const char *path, uint32_t flags,
+                               ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !e || !out || !path) return NGPU_EINVAL;
+  return guarded([&]() -> int {
+    if (e->cfg.fs_version != 6)
+      return fail(e, NGPU_EINVAL, "dict extend takes RAFS v6 bootstraps (FsVersion %u engine)",
+                  e->cfg.fs_version);
+    struct stat st;
+    if (stat(path, &st) != 0) return fail(e, NGPU_EIO, "stat chunk dict %s", path);
+    std::vector<uint8_t> recs, blobs;
+    if (int rc = read_dict_bootstrap(e, path, (uint64_t)st.st_size, &recs, &blobs)) return rc;
+    return dict_extend(e, base, recs.data(), recs.size() / 80, blobs.data(),
+                       (uint32_t)(blobs.size() / 256), out);
+  });
+}
+
+int ngpu_dict_info_get(const ngpu_dict *d, ngpu_dict_info *out) {
+  if (!d || !out) return NGPU_EINVAL;
+  memset(out, 0, sizeof *out);
+  const ngpu_dict *p = d->parts.empty() ? d : d->parts[0];
+  out->entries = d->dev.m;
+  out->blobs = d->dev.n_blobs;
+  if (p->st) {
+    out->record_capacity = p->st->rec_cap;
+    out->table_capacity = p->st->table_cap;
+  }
+  out->shares_base_storage = p->shares_base;
+  return 0;
 }
 
 int ngpu_dict_create_device(ngpu_engine *e, const uint8_t *d_digests, const uint32_t *d_usize,

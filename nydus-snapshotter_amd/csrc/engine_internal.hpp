@@ -51,17 +51,43 @@ struct ngpu_pack_bufs {
   BlobWindows win;              // the blob stream's gather windows (ngpu_pack_finish)
 };
 
-// A chunk dict ([nydus v2.3.0] HashChunkDict): HBM-resident, read-only once
-// built, reference counted (the engine's default slot, its open cache, every
-// pack using it and the caller each hold one).
+namespace ngpu {
+// What dict handles sit on: the records, the hash table and the host placement
+// rows of one allocation, reference counted by its handles.  A dict made by
+// create / open has a storage of its own, exactly its size; ngpu_dict_extend
+// puts a new handle on the base's storage when the base is the newest handle
+// there and the storage has room (dict_grow_plan.hpp), else on a larger one.
+// Slots below `used` are never written again; the last handle to go frees it.
+struct DictStorage {
+  std::atomic<int> refs{1};
+  int device = 0;
+  DictRec *rec = nullptr;      // rec_cap records (HBM)
+  uint64_t *table = nullptr;   // table_cap slots (HBM)
+  uint64_t rec_cap = 0, table_cap = 0;
+  DictPlace *place = nullptr;  // rec_cap rows (host, untouched past `used`), null: none kept
+  uint64_t used = 0;           // highest record slot ever reserved (mu)
+  std::mutex mu;               // reserving [used, used + k)
+};
+}  // namespace ngpu
+
+// A chunk dict ([nydus v2.3.0] HashChunkDict): HBM-resident, immutable per
+// handle (ngpu_dict_extend returns a new one), reference counted (the engine's
+// default slot, its open cache, every pack using it and the caller each hold
+// one).
 struct ngpu_dict {
   std::atomic<int> refs{1};
   int device = 0;
   uint32_t digester = 0, chunk_size = 0;
-  ngpu::DictDevice dev;                // device arrays + hash table
-  std::vector<void *> allocs;          // device allocations owned
+  // device arrays + hash table: rec / table / mask point into `st`, m is this
+  // handle's own count
+  ngpu::DictDevice dev;
+  // node dicts: the global handle's storage holds placement rows only
+  ngpu::DictStorage *st = nullptr;     // one reference
+  bool has_place = false;              // st->place[0, dev.m) are this handle's rows
+  bool shares_base = false;            // made by an in-place extend
   std::vector<uint8_t> blob_table;     // 256-B RAFS v6 blob records (inner-index order)
-  std::vector<ngpu::DictPlace> place;  // per entry: compressed placement (empty: unknown)
+  // per entry: compressed placement (null: unknown), dev.m rows
+  const ngpu::DictPlace *place() const { return has_place && st ? st->place : nullptr; }
   // identity of the bootstrap file it was opened from (ngpu_dict_open cache)
   std::string path;
   uint64_t st_dev = 0, st_ino = 0, st_size = 0;
@@ -314,6 +340,22 @@ uint64_t next_pow2(uint64_t x);
 // From 80-B RAFS v6 records in host memory on engine e's device (own stream, no lock).
 int dict_from_records(ngpu_engine *e, const uint8_t *recs, uint64_t m, const uint8_t *blobs,
                       uint32_t n_blobs, ngpu_dict **out, const uint32_t *gids);
+// What ngpu_dict_extend and the node extend share: check k more records against
+// base (an engine dict or a node dict's global handle), *nb_out = the result's
+// blob count and *with_table whether it keeps a blob table.
+int dict_extend_check(ngpu_engine *e, const ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                      const uint8_t *blobs, uint32_t n_blobs, uint32_t *nb_out, bool *with_table);
+// A new handle of base's entries followed by k records (80 B each; blob0 is
+// added to their blob indices, gids: their global ids, null = base's count +
+// position), in place or on a new storage; place: keep their placement rows.
+// The handle's blob count is nb; its blob table is left to the caller.
+int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                        uint32_t blob0, uint32_t nb, const uint32_t *gids, bool place,
+                        ngpu_dict **out);
+// A storage with placement rows only (node dicts' global handles) / k more rows.
+int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                      ngpu_dict *out);
+void storage_unref(DictStorage *st);
 int read_dict_bootstrap(ngpu_engine *e, const char *path, uint64_t file_size,
                         std::vector<uint8_t> *recs_out, std::vector<uint8_t> *blobs_out,
                         uint64_t *table_at = nullptr);

@@ -29,6 +29,7 @@
 // and the whole step enqueues without a host wait.
 #include <dlfcn.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
 
@@ -286,10 +287,10 @@ int node_dict_build(ngpu_node *node, const uint8_t *recs, uint64_t m, const uint
   d->routed = !d->replicated && routed && node->peer_ok;
   d->dev.m = m;
   d->dev.n_blobs = nb;
-  d->place.resize(m);
-  for (uint64_t i = 0; i < m; ++i) {
-    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-    d->place[i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+  // the global handle sits on a storage of placement rows only
+  if (int rc = dict_place_extend(e0, nullptr, recs, m, d)) {
+    dict_unref(d);
+    return rc;
   }
   if (blobs && n_blobs) d->blob_table.assign(blobs, blobs + 256ull * n_blobs);
   const uint32_t W = (uint32_t)node->eng.size();
@@ -313,12 +314,73 @@ int node_dict_build(ngpu_node *node, const uint8_t *recs, uint64_t m, const uint
     if ((rc = dict_from_records(e, pr, pm, blobs, nb, &p, d->replicated ? nullptr : gid[o].data())))
       break;
     p->dev.n_blobs = nb;
-    p->place.clear();  // the global table (d->place) answers the writer
+    // the global table (d's storage) answers the writer
+    free(p->st->place);
+    p->st->place = nullptr;
+    p->has_place = false;
     d->parts.push_back(p);
   }
   if (rc) {
     dict_unref(d);
     return rc;
+  }
+  *out = d;
+  return 0;
+}
+
+// base followed by k more records: every part extended in place or onto a new
+// storage as its own plan says (a partitioned part gets the records it owns,
+// with global ids m + position; a replica gets all of them), the global
+// placement rows likewise.
+int node_dict_extend(ngpu_node *node, ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                     const uint8_t *blobs, uint32_t n_blobs, ngpu_dict **out) {
+  ngpu_engine *e0 = node->eng[0];
+  const uint32_t W = (uint32_t)node->eng.size();
+  if (base->parts.empty())
+    return fail(e0, NGPU_EINVAL, "node dict extend: not a node dict (ngpu_dict_extend takes it)");
+  if (base->parts.size() != W) return fail(e0, NGPU_EINVAL, "node dict extend: dict of another node");
+  for (uint32_t o = 0; o < W; ++o)
+    if (base->parts[o]->device != node->eng[o]->device)
+      return fail(e0, NGPU_EINVAL, "node dict extend: dict of another node");
+  if (int rc = dict_check(e0, base)) return rc;
+  uint32_t nb = 0;
+  bool with_table = false;
+  if (int rc = dict_extend_check(e0, base, recs, k, blobs, n_blobs, &nb, &with_table)) return rc;
+  const uint64_t m = base->dev.m;
+  ngpu_dict *d = new ngpu_dict();
+  d->device = base->device;
+  d->digester = base->digester;
+  d->chunk_size = base->chunk_size;
+  d->replicated = base->replicated;
+  d->routed = base->routed;
+  d->dev.m = m + k;
+  d->dev.n_blobs = nb;
+  int rc = dict_place_extend(e0, base, recs, k, d);
+  std::vector<std::vector<uint8_t>> part_recs(W);
+  std::vector<std::vector<uint32_t>> gid(W);
+  if (!rc && !d->replicated) {
+    for (uint64_t i = 0; i < k; ++i) {
+      const uint32_t o = owner_of(recs + 80 * i, W);
+      part_recs[o].insert(part_recs[o].end(), recs + 80 * i, recs + 80 * (i + 1));
+      gid[o].push_back((uint32_t)(m + i));
+    }
+  }
+  for (uint32_t o = 0; o < W && !rc; ++o) {
+    ngpu_dict *p = nullptr;
+    const uint8_t *pr = d->replicated ? recs : part_recs[o].data();
+    const uint64_t pk = d->replicated ? k : gid[o].size();
+    if ((rc = dict_extend_records(node->eng[o], base->parts[o], pr, pk, base->dev.n_blobs, nb,
+                                  d->replicated ? nullptr : gid[o].data(), false, &p)))
+      break;
+    d->parts.push_back(p);
+  }
+  if (rc) {
+    dict_unref(d);
+    return rc;
+  }
+  if (with_table) {
+    d->blob_table = base->blob_table;
+    if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
   }
   *out = d;
   return 0;
@@ -721,6 +783,18 @@ int ngpu_node_dict_create(ngpu_node *node, const void *records, uint64_t n,
   return guarded([&] {
     return node_dict_build(node, (const uint8_t *)records, n, (const uint8_t *)blob_table, n_blobs,
                            mode, out);
+  });
+}
+
+int ngpu_node_dict_extend(ngpu_node *node, ngpu_dict *base, const void *records, uint64_t n,
+                          const void *blob_table, uint32_t n_blobs, uint32_t flags,
+                          ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !node || !out || (n && !records) || (n_blobs && !blob_table))
+    return NGPU_EINVAL;
+  return guarded([&] {
+    return node_dict_extend(node, base, (const uint8_t *)records, n, (const uint8_t *)blob_table,
+                            n_blobs, out);
   });
 }
 

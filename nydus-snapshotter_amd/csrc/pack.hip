@@ -564,9 +564,11 @@ int make_writer(ngpu_pack *p, const ngpu_blob_options &opt, ngpu_write_fn w, voi
   if (nrec) memcpy(dict.data(), rec, nrec * sizeof(RafsV6BlobInfo));
   const DictPlace *place = nullptr;
   uint64_t nplace = 0;
-  if (p->dict && !p->dict->place.empty()) {
-    place = p->dict->place.data();
-    nplace = p->dict->place.size();
+  // the rows live on the storage the handle sits on, which later handles may
+  // have grown: this pack's dict ends at its own entry count
+  if (p->dict && p->dict->place()) {
+    place = p->dict->place();
+    nplace = p->dict->dev.m;
   }
   out->reset(new BlobWriter(o, w, ctx, std::move(dict), place, nplace));
   (*out)->set_cancel(p->cancel);

@@ -81,7 +81,16 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # Verity (additive in ABI 7)
            "ngpu_verity_layout", "ngpu_verity_device", "ngpu_verity_image",
            # Verity verify (additive in ABI 7)
-           "ngpu_verity_verify_tree_device", "ngpu_verity_verify_data_device", "ngpu_verity_verify_image"]
+           "ngpu_verity_verify_tree_device", "ngpu_verity_verify_data_device", "ngpu_verity_verify_image",
+           # dict extend (additive in ABI 7)
+           "ngpu_dict_extend", "ngpu_dict_extend_bootstrap", "ngpu_node_dict_extend",
+           "ngpu_dict_info_get"]
+
+class NgpuDictInfo(ctypes.Structure):
+    _fields_ = [("entries", ctypes.c_uint64), ("blobs", ctypes.c_uint64),
+                ("record_capacity", ctypes.c_uint64), ("table_capacity", ctypes.c_uint64),
+                ("shares_base_storage", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
 
 LAYER_STATS_DTYPE = np.dtype([("chunks", "<u8"), ("new_chunks", "<u8"), ("intra_chunks", "<u8"),
                               ("dict_chunks", "<u8"), ("new_bytes", "<u8"), ("own_blob_index", "<u4"),
@@ -315,6 +324,10 @@ def lib():
     L.ngpu_node_dict_create.argtypes = [vp, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_owner.argtypes = [vp, vp]
     L.ngpu_node_owner.restype = u32
+    L.ngpu_dict_extend.argtypes = [vp, vp, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
+    L.ngpu_dict_extend_bootstrap.argtypes = [vp, vp, ctypes.c_char_p, u32, ctypes.POINTER(vp)]
+    L.ngpu_node_dict_extend.argtypes = [vp, vp, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
+    L.ngpu_dict_info_get.argtypes = [vp, ctypes.POINTER(NgpuDictInfo)]
     L.ngpu_node_pack_open.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
     L.ngpu_node_process_device.argtypes = [vp, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp]
     L.ngpu_node_process_step.argtypes = [vp, vp, ctypes.POINTER(NgpuNodePart), u32, u32]
@@ -691,10 +704,12 @@ DEFAULT_DICT = object()  # "the engine's default dict" (the calls without a dict
 class ChunkDict:
     """A chunk dict handle (ngpu_dict*): the HBM-resident HashChunkDict of one
     ChunkDictPath (or of arrays), reference counted.  A pack opened with it
-    keeps its own reference, so releasing the handle never disturbs a pack."""
+    keeps its own reference, so releasing the handle never disturbs a pack.
+    A handle never changes: extend() returns a new one."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, engine=None):
         self._h = handle
+        self._eng = engine  # the Engine that made it (extend needs one)
 
     @property
     def handle(self) -> int:
@@ -716,6 +731,44 @@ class ChunkDict:
 
     def __exit__(self, *a):
         self.release()
+
+    def info(self) -> dict:
+        """ngpu_dict_info_get: entries, blobs, the capacities of the storage the
+        handle sits on and whether an in-place extend made it."""
+        x = NgpuDictInfo()
+        rc = lib().ngpu_dict_info_get(self._h, ctypes.byref(x))
+        if rc:
+            raise NgpuError(rc, "dict_info")
+        return {"entries": x.entries, "blobs": x.blobs, "record_capacity": x.record_capacity,
+                "table_capacity": x.table_capacity,
+                "shares_base_storage": bool(x.shares_base_storage)}
+
+    def _engine(self):
+        if self._eng is None or not self._eng._h:
+            raise ValueError("this dict was not made by an open Engine (Node.dict_extend for node dicts)")
+        return self._eng
+
+    def extend(self, records, blobs=None) -> "ChunkDict":
+        """ngpu_dict_extend: a new dict of this one's entries followed by the
+        80-B RAFS v6 chunk records (their blob indices count from this dict's
+        blob count; blobs: their 256-B blob records).  This handle stays as it is."""
+        e = self._engine()
+        r = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+        b = None if blobs is None or not len(blobs) else np.ascontiguousarray(blobs).view(np.uint8).reshape(-1)
+        h = ctypes.c_void_p()
+        e._check(lib().ngpu_dict_extend(e._h, self._h, _ptr(r), r.size // 80, _ptr(b),
+                                        0 if b is None else b.size // 256, 0, ctypes.byref(h)),
+                 "dict_extend")
+        return ChunkDict(h, e)
+
+    def extend_bootstrap(self, path: str) -> "ChunkDict":
+        """ngpu_dict_extend_bootstrap: extend() with the chunk table and blob
+        table of a RAFS v6 bootstrap file (checked as dict_open checks it)."""
+        e = self._engine()
+        h = ctypes.c_void_p()
+        e._check(lib().ngpu_dict_extend_bootstrap(e._h, self._h, path.encode(), 0, ctypes.byref(h)),
+                 "dict_extend_bootstrap")
+        return ChunkDict(h, e)
 
     def probe_device(self, d_digests: int, stride: int, n: int, d_hits: int, stream: int = 0):
         rc = lib().ngpu_dict_probe(self._h, ctypes.c_void_p(d_digests), stride, n,
@@ -802,7 +855,7 @@ class Engine:
         """ngpu_dict_open: load (or reuse, if unchanged) a RAFS v6 chunk-dict bootstrap."""
         h = ctypes.c_void_p()
         self._check(lib().ngpu_dict_open(self._h, path.encode(), ctypes.byref(h)), "dict_open")
-        return ChunkDict(h)
+        return ChunkDict(h, self)
 
     def dict_create(self, records, blobs=None) -> ChunkDict:
         """From 80-B RAFS v6 chunk records (table order) + 256-B blob records."""
@@ -812,7 +865,7 @@ class Engine:
         self._check(lib().ngpu_dict_create(self._h, _ptr(r), r.size // 80, _ptr(b),
                                            0 if b is None else b.size // 256, ctypes.byref(h)),
                     "dict_create")
-        return ChunkDict(h)
+        return ChunkDict(h, self)
 
     def dict_create_device(self, d_digests: int, d_usize: int, d_blob: int, d_index: int, n: int,
                            n_blobs: int, d_uoff: int = 0, d_gid: int = 0) -> ChunkDict:
@@ -822,7 +875,7 @@ class Engine:
         self._check(lib().ngpu_dict_create_device_gid(
             self._h, self._vp(d_digests), self._vp(d_usize), self._vp(d_blob), self._vp(d_index),
             self._vp(d_uoff), self._vp(d_gid), n, n_blobs, ctypes.byref(h)), "dict_create_device")
-        return ChunkDict(h)
+        return ChunkDict(h, self)
 
     def set_dict(self, d):
         self._check(lib().ngpu_set_dict(self._h, _dict_arg(d)), "set_dict")
@@ -1355,6 +1408,17 @@ class Node:
         self._err(lib().ngpu_node_dict_create(self._h, _ptr(r), r.size // 80, _ptr(b),
                                               0 if b is None else b.size // 256, mode, ctypes.byref(h)),
                   "node_dict_create")
+        return ChunkDict(h)
+
+    def dict_extend(self, base: ChunkDict, records, blobs=None) -> ChunkDict:
+        """ngpu_node_dict_extend: a new node dict of base's entries followed by
+        the records (each part gets those it owns, a replica all of them)."""
+        r = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+        b = None if blobs is None or not len(blobs) else np.ascontiguousarray(blobs).view(np.uint8).reshape(-1)
+        h = ctypes.c_void_p()
+        self._err(lib().ngpu_node_dict_extend(self._h, base._h, _ptr(r), r.size // 80, _ptr(b),
+                                              0 if b is None else b.size // 256, 0, ctypes.byref(h)),
+                  "node_dict_extend")
         return ChunkDict(h)
 
     def pack(self, dict=None, retain: bool = False) -> "PackWriter":

@@ -18,7 +18,7 @@ usage:
   python -m nydus_gpu.inspect --tree FILE     # JSON dump of the inode tree
   python -m nydus_gpu.inspect --diff A B      # exit 0 iff the chunk sets match
   python -m nydus_gpu.inspect --diff --tree A B  # exit 0 iff the trees match
-  python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP] [--chunk-size N] [--digester D]
+  python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP]... [--chunk-size N] [--digester D]
                                               # re-digest STREAM's chunks on the GPU; exit 1 if any is bad
   python -m nydus_gpu.inspect --verity IMAGE [--append]
                                               # the dm-verity tree of a block image; prints its options line
@@ -32,6 +32,9 @@ FILE may be a bootstrap (image.boot) or a whole Pack output stream.
 the stream's image.boot is read from its image.blob, inflated, hashed on the GPU
 and compared with the record's digest; records of other blobs must resolve in
 the `--dict` chunk-dict bootstrap (without one they are counted as skipped).
+Several `--dict` are folded into one dict in the order given (the first is
+opened, each further one appended with ChunkDict.extend_bootstrap), as a
+conversion run folds each converted image into its chunk dict.
 The digester, chunk size and RAFS version default to the stream's own; the
 report is printed as JSON.
 
@@ -144,9 +147,10 @@ def diff(a: dict, b: dict, fields=("digest", "blob_id", "uncompressed_size")) ->
     return [("-", k) for k in sorted(ka - kb)] + [("+", k) for k in sorted(kb - ka)]
 
 
-def check(path: str, dict_path: str = None, chunk_size: int = 0, digester: str = None,
+def check(path: str, dict_path=None, chunk_size: int = 0, digester: str = None,
           max_bad: int = 64) -> dict:
-    """Engine.check of the stream in `path` on GPU 0 (the report dict)."""
+    """Engine.check of the stream in `path` on GPU 0 (the report dict).
+    dict_path: a chunk-dict bootstrap, or a list of them folded into one dict."""
     from ._lib import Engine
     data = np.fromfile(path, np.uint8)
     boot = bootstrap_bytes(data)
@@ -159,8 +163,13 @@ def check(path: str, dict_path: str = None, chunk_size: int = 0, digester: str =
         flags, cs = int(d["flags"]), int(d["chunk_size"])
     with Engine(device=0, digester=digester or ("sha256" if flags & 0x8 else "blake3"),
                 chunk_size=chunk_size or cs, fs_version=6 if v6 else 5) as eng:
-        dct = eng.dict_open(dict_path) if dict_path else None
+        paths = [dict_path] if isinstance(dict_path, str) else list(dict_path or [])
+        dct = eng.dict_open(paths[0]) if paths else None
         try:
+            for p in paths[1:]:
+                grown = dct.extend_bootstrap(p)
+                dct.release()
+                dct = grown
             return eng.check(data, dict=dct, max_bad=max_bad)
         finally:
             if dct is not None:
@@ -229,7 +238,8 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nydus_gpu.inspect")
     ap.add_argument("files", nargs="*")
     ap.add_argument("--check", metavar="STREAM", help="re-digest a Pack output stream's chunks on the GPU")
-    ap.add_argument("--dict", metavar="BOOTSTRAP", help="--check: chunk-dict bootstrap for DICT records")
+    ap.add_argument("--dict", metavar="BOOTSTRAP", action="append",
+                    help="--check: chunk-dict bootstrap for DICT records (repeat to fold several into one dict)")
     ap.add_argument("--chunk-size", type=lambda x: int(x, 0), default=0, help="--check: engine chunk size")
     ap.add_argument("--digester", choices=("blake3", "sha256"), help="--check: engine digester")
     ap.add_argument("--verity", metavar="IMAGE", help="dm-verity tree of a block image on the GPU")

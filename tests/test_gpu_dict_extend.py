@@ -1,0 +1,798 @@
+"""Dict extend (ngpu_dict_extend / ngpu_node_dict_extend, csrc/dict.hip) on the GPU.
+
+The expectation everywhere is the concatenation the header defines: the base's
+records followed by the new ones with their blob indices shifted by the base's
+blob count -- as one ngpu_dict_create over all rows answers, and as the CPU
+model / oracle answers when fed those rows.
+
+  1  every dedup path of the collision matrix under extend(create(rows[:c]),
+     rows[c:]) for every cut c of the case's dict rows, and three double cuts
+  2  the dict's own table: a tag-collision chain, duplicate digests and a
+     chain that wraps past the top of the table, split over base and extensions
+  3  share / fork as dict_grow_plan says, and older handles blind to appends
+  4  in-place appends while dedup kernels probe the base on another stream
+  5  Pack / Check / bootstrap flow, the blob-table rule, refused bootstraps
+  6  node dicts (partitioned copy / routed, replicated)
+  7  inspect --check --dict A --dict B
+"""
+import json
+import os
+import subprocess
+import sys
+import threading
+
+import numpy as np
+import pytest
+
+import dedup_cases as dc
+import nydus_gpu
+from nydus_gpu import rafs
+from conftest import ROOT
+from test_dedup_cases import DICT, NEW, NONE, expect, model_dedup
+
+pytestmark = pytest.mark.gpu
+
+GRID = nydus_gpu.FLAG_GRID_STAGES
+STAT_FIELDS = ("chunks", "new_chunks", "intra_chunks", "dict_chunks", "new_bytes",
+               "uncompressed_size", "own_blob_index", "blobs")
+FLAG_BLAKE3, FLAG_SHA256 = 0x4, 0x8
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
+
+
+def _recs(dd, ds, db, di, duoff):
+    r = np.zeros(len(ds), rafs.CHUNK_INFO_DTYPE)
+    r["block_id"], r["uncompressed_size"], r["blob_index"] = dd, ds, db
+    r["index"], r["uncompressed_offset"] = di, duoff
+    r["compressed_offset"] = np.arange(len(ds), dtype=np.uint64) * 4096 + 17
+    r["compressed_size"] = 4000
+    r["flags"] = 1
+    return r
+
+
+class _borrowed:
+    """A view of dict handle d bound to engine `eng` that never releases it."""
+
+    def __init__(self, d, eng):
+        self.view = nydus_gpu.ChunkDict(d._h, eng)
+
+    def __enter__(self):
+        return self.view
+
+    def __exit__(self, *a):
+        self.view._h = None
+
+
+def _pow2(x):
+    p = 1
+    while p < x:
+        p *= 2
+    return p
+
+
+def _fork_caps(m, k):
+    """dict_grow_plan's fork: record and table capacity for m + k entries."""
+    n = m + k
+    want = n + max(k, n // 2)
+    return want, _pow2(2 * want + 16)
+
+
+def _first_rows(dd):
+    first = {}
+    for j in range(len(dd)):
+        first.setdefault(bytes(dd[j]), j)
+    return first
+
+
+def _probe(d, d_q, nq):
+    """ngpu_dict_probe of handle d over nq 32-byte digests -> HIT_DTYPE array."""
+    import torch
+    hits = torch.zeros(nq * 24, dtype=torch.uint8, device="cuda")
+    d.probe_device(d_q.data_ptr(), 32, nq, hits.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return hits.cpu().numpy().view(nydus_gpu.HIT_DTYPE)
+
+
+def _expect_hits(rows, q):
+    """Plain first-occurrence scan of the 80-B rows for every query digest."""
+    first = _first_rows(rows["block_id"])
+    exp = np.zeros(len(q), nydus_gpu.HIT_DTYPE)
+    for i in range(len(q)):
+        j = first.get(bytes(q[i]))
+        if j is None:
+            exp[i]["entry"] = nydus_gpu.MISS
+        else:
+            r = rows[j]
+            exp[i] = (j, r["index"], r["blob_index"], r["uncompressed_size"], r["uncompressed_offset"])
+    return exp
+
+
+def _concat(segments, with_tables):
+    """The rows a chain of extends over `segments` (80-B record arrays) stands
+    for: segment s's blob indices shifted by the blob count before it (with
+    tables: each segment brings its table's count; without: max index + 1)."""
+    out, shift = [], 0
+    for seg, nb in segments:
+        r = seg.copy()
+        r["blob_index"] += shift
+        out.append(r)
+        shift += nb if with_tables else (int(seg["blob_index"].max()) + 1 if len(seg) else 0)
+    return np.concatenate(out), shift
+
+
+# ---- 1: every dedup path, every cut ---------------------------------------------
+_TABLES = {}
+
+
+def _table(nb):
+    if nb not in _TABLES:
+        _TABLES[nb] = rafs.make_blob_table([f"{i:064x}" for i in range(nb)], dc.CHUNK_SIZE)
+    return _TABLES[nb]
+
+
+def _case_expect(case, base, rows):
+    """model_dedup over `rows` (the case's dict rows, blob indices shifted per
+    segment).  The shift changes nothing but blob numbering, so the decisions
+    come from the model run on the unshifted rows (`base`, once per case) and
+    the real blob indices from the order of first use -- a shortcut that
+    test_extend_every_cut checks against model_dedup itself on three cuts of
+    every case."""
+    exp, st = base
+    exp, st = exp.copy(), dict(st)
+    hit = exp["kind"] == DICT
+    label = np.full(case.n, 1 << 40, np.int64)  # the layer's own blob
+    label[hit] = rows["blob_index"][exp["ref"][hit].astype(np.int64)]
+    uniq, firsts = np.unique(label, return_index=True)
+    rank = np.empty(len(uniq), np.int64)
+    rank[np.argsort(firsts)] = np.arange(len(uniq))
+    real = rank[np.searchsorted(uniq, label)]
+    has_new = bool((exp["kind"] == NEW).any())
+    exp["blob_index"] = real
+    if not has_new:
+        assert hit.all()
+    st["blobs"] = len(uniq)
+    st["own_blob_index"] = int(real[np.flatnonzero(~hit)[0]]) if has_new else NONE
+    dict_blob = np.zeros(case.n, np.uint32)
+    dict_blob[hit] = rows["blob_index"][exp["ref"][hit].astype(np.int64)]
+    return exp, st, dict_blob
+
+
+def _dedup(eng, call, case, d_ch, rec0):
+    """One dedup call over fresh records -> (records, stats tuple)."""
+    import torch
+    out = _dev(rec0)
+    if call == "layers":
+        d_first = torch.from_numpy(np.asarray([0, case.n], np.int64)).cuda()
+        d_st = torch.zeros(nydus_gpu.LAYER_STATS_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        eng.dedup_layers_device(d_ch.data_ptr(), case.n, out.data_ptr(), d_first.data_ptr(), 1, d_st.data_ptr())
+        torch.cuda.synchronize()
+        st = d_st.cpu().numpy().view(nydus_gpu.LAYER_STATS_DTYPE)[0]
+    else:
+        st = eng.dedup_device(d_ch.data_ptr(), case.n, out.data_ptr(), want_stats=True)
+    torch.cuda.synchronize()
+    return out.cpu().numpy().view(nydus_gpu.RESULT_DTYPE), tuple(int(st[f]) for f in STAT_FIELDS)
+
+
+def _check_dedup(tag, case, got, stats, exp, est, dict_blob):
+    assert np.array_equal(got["digest"], case.digests), tag
+    for f in ("kind", "ref", "index", "blob_index", "uncompressed_offset"):
+        bad = np.flatnonzero(got[f] != exp[f])
+        assert not len(bad), f"{tag}: {f} differs on {len(bad)} chunks, first {bad[0]}: " \
+                             f"got {got[f][bad[0]]}, expected {exp[f][bad[0]]}"
+    assert np.array_equal(got["dict_blob"], dict_blob), tag
+    assert stats == tuple(est[f] for f in STAT_FIELDS), (tag, stats, est)
+
+
+def _every_cut(path, case, fs, flags, call):
+    import torch
+    m, nb = case.m, case.dict[5]
+    dd, ds, db, di, duoff, _ = case.dict
+    rows0 = _recs(dd, ds, db, di, duoff)
+    with_tables = fs == 6  # v6: every segment brings its blob table; v5: blob counts only
+    base_model = expect(case)
+    cuts = [(c,) for c in range(m + 1)] + [(m // 4, m // 2), (1, m - 1), (m // 3, m // 3)]
+    model_at = {(0,), (m // 2,), (m // 4, m // 2)}
+    ch = np.zeros(case.n, nydus_gpu.CHUNK_DTYPE)
+    ch["length"] = case.lengths
+    ch["file_index"] = np.arange(case.n)
+    rec0 = np.zeros(case.n, nydus_gpu.RESULT_DTYPE)
+    rec0["digest"] = case.digests
+    rec0["kind"] = nydus_gpu.DIGESTED
+    rec0["index"] = rec0["blob_index"] = rec0["dict_blob"] = 0xDEADBEEF
+    rec0["ref"] = rec0["uncompressed_offset"] = 0xDEADBEEFDEADBEEF
+    d_ch, d_q = _dev(ch), _dev(case.digests)
+    tbl = _table(nb) if with_tables else None
+    eng = nydus_gpu.Engine(chunk_size=dc.CHUNK_SIZE, fs_version=fs, flags=flags)
+    try:
+        for cut in cuts:
+            tag = f"{path} {case.name} fs v{fs} cut {cut}"
+            edges = (0,) + cut + (m,)
+            segs = [(rows0[a:b], nb) for a, b in zip(edges[:-1], edges[1:])]
+            rows, total = _concat(segs, with_tables)
+            exp, est, dict_blob = _case_expect(case, base_model, rows)
+            if cut in model_at:
+                mexp, mst = model_dedup(case.digests, case.lengths, rows["block_id"], rows["uncompressed_size"],
+                                        rows["blob_index"], rows["index"], rows["uncompressed_offset"], case.align)
+                for f in ("kind", "ref", "index", "blob_index", "uncompressed_offset"):
+                    assert np.array_equal(exp[f], mexp[f]), (tag, f)
+                assert est == mst, (tag, est, mst)
+            hexp = _expect_hits(rows, case.digests) if cut in model_at else None
+            # the chain of extends
+            d = eng.dict_create(segs[0][0], tbl)
+            for seg, _ in segs[1:]:
+                g = d.extend(seg, tbl)
+                d.release()
+                d = g
+            one = eng.dict_create(rows, _table(total) if with_tables else None)
+            assert d.entries == one.entries == m
+            assert d.info()["blobs"] == one.info()["blobs"] == total, tag
+            outs = []
+            for h in (d, one):
+                eng.set_dict(h)
+                got, stats = _dedup(eng, call, case, d_ch, rec0)
+                _check_dedup(tag, case, got, stats, exp, est, dict_blob)
+                hits = torch.zeros(case.n * 24, dtype=torch.uint8, device="cuda")
+                eng.dict_probe_device(d_q.data_ptr(), 32, case.n, hits.data_ptr())
+                torch.cuda.synchronize()
+                outs.append((got.tobytes(), stats, hits.cpu().numpy().tobytes()))
+            assert outs[0] == outs[1], f"{tag}: differs from the single-create dict"
+            if hexp is not None:
+                assert outs[0][2] == hexp.tobytes(), f"{tag}: probe hits differ from the row scan"
+            eng.set_dict(None)
+            d.release()
+            one.release()
+        eng.device_status()
+    finally:
+        eng.close()
+
+
+PARAMS = [(p, n) for p in ("lds256", "lds1024", "small", "grid") for n in dc.PATH_N[p]]
+
+
+@pytest.mark.parametrize("path,n", PARAMS, ids=[f"{p}-{n}" for p, n in PARAMS])
+def test_extend_every_cut(path, n):
+    """extend(create(rows[:c]), rows[c:]) for every cut c of the case's dict rows
+    (dict_duprow's two rows, the wildcard row and the tagchain end up on both
+    sides of a cut) and three double cuts: every record field, every stats field
+    and the probe hits equal the model on the concatenation and, byte for byte,
+    what a single dict_create over it gives."""
+    for align, fs in ((4096, 6), (1, 5)):
+        variants = [(False, "layers" if path == "small" else "one")]
+        if path == "small":
+            variants.append((True, "one"))  # > 1023 dict blobs: ngpu_dedup_device leaves the LDS kernel
+        for many, call in variants:
+            case = dc.get("mixed", n, align, True, many)
+            if not case.m:  # n = 1, 2: no room for a dict class
+                continue
+            _every_cut(path, case, fs, GRID if path == "grid" else 0, call)
+
+
+# ---- 2: the dict's own table ------------------------------------------------------
+def _words_homed(rng, slot, mask, count):
+    found = []
+    while len(found) < count:
+        w = rng.integers(0, np.iinfo(np.uint64).max, 1 << 18, dtype=np.uint64, endpoint=True)
+        found.extend(int(x) for x in w[(np.multiply(w, np.uint64(dc.GOLDEN)) & np.uint64(mask)) == np.uint64(slot)])
+    return list(dict.fromkeys(found))[:count]
+
+
+def test_extend_table_chains_duplicates_and_wrap():
+    """The construction of test_probe_walks_tag_collisions_and_keeps_first_row
+    (4,096 rows, 14 sharing bucket words and tag, later and earlier duplicates)
+    cut at 650 and 3000: b = create(rows[:650]), x1 = extend(b, rows[650:3000])
+    (a new storage), x2 = extend(x1, rows[3000:]) (in place).  The collision
+    chain, the pairs 300 / 900 and 50 / 700 straddle b and x1; 800 / 3500
+    straddles x1 and x2; 3100 / 3600 are two new rows of one digest in one
+    append.  Seven rows homed at table_capacity - 2 wrap to slot 0 with members
+    in all three parts.  Expected entries: a first-occurrence scan."""
+    rng = np.random.default_rng(0x7A6)
+    m, c0, c1 = 4096, 650, 3000
+    rec_cap, table_cap = _fork_caps(c0, c1 - c0)
+    assert rec_cap >= m and 2 * m + 16 <= table_cap  # so the second extend is in place
+    dd = rng.integers(0, 256, (m, 32), dtype=np.uint8)
+    coll = [100, 200, 300, 400, 500, 600, 700, 800, 1000, 1100, 1200, 1300, 3100, 3200]
+    for r in coll:
+        dd[r, :12] = dd[100, :12]
+    wrap = [10, 20, 660, 670, 3010, 3020, 3030]
+    for r, w in zip(wrap, _words_homed(rng, table_cap - 2, table_cap - 1, len(wrap))):
+        dd[r, :8] = np.frombuffer(np.uint64(w).tobytes(), np.uint8)
+    assert (dc.home_slot(dd[wrap], table_cap - 1) == table_cap - 2).all()
+    dd[900], dd[50], dd[3500], dd[3600] = dd[300], dd[700], dd[800], dd[3100]
+    miss_chain = dd[100].copy()
+    miss_chain[12:] = rng.integers(0, 256, 20, dtype=np.uint8)
+    miss_wrap = dd[3010].copy()
+    miss_wrap[8:] = rng.integers(0, 256, 24, dtype=np.uint8)  # walks the wrapped chain to its end
+    near = dd[400].copy()
+    near[31] ^= 1
+    q = np.stack([dd[r] for r in coll + wrap + [900, 50, 3500, 3600]] + [miss_chain, miss_wrap, near] +
+                 [rng.integers(0, 256, 32, dtype=np.uint8) for _ in range(8)] +
+                 [dd[r] for r in rng.choice(m, 96, replace=False)])
+    rows = _recs(dd, (np.arange(m) % 5 + 1) * 4096, np.zeros(m, np.uint32), np.arange(m) * 7 + 3,
+                 np.arange(m, dtype=np.uint64) * 4096)
+    segs = [(rows[:c0], 1), (rows[c0:c1], 1), (rows[c1:], 1)]
+    d_q = _dev(q)
+    with nydus_gpu.Engine(chunk_size=0x10000) as eng:
+        b = eng.dict_create(rows[:c0])
+        x1 = b.extend(rows[c0:c1])
+        x2 = x1.extend(rows[c1:])
+        i1, i2 = x1.info(), x2.info()
+        assert (i1["record_capacity"], i1["table_capacity"], i1["shares_base_storage"]) == (rec_cap, table_cap, False)
+        assert (i2["record_capacity"], i2["table_capacity"], i2["shares_base_storage"]) == (rec_cap, table_cap, True)
+        assert (b.entries, x1.entries, x2.entries) == (c0, c1, m)
+        for k, h in ((1, b), (2, x1), (3, x2)):  # after every append: each handle answers for its own rows
+            part, _ = _concat(segs[:k], False)
+            exp = _expect_hits(part, q)
+            got = _probe(h, d_q, len(q))
+            assert np.array_equal(got["entry"], exp["entry"]), (k, got["entry"][:32], exp["entry"][:32])
+            assert got.tobytes() == exp.tobytes(), k
+            one = eng.dict_create(part)
+            assert _probe(one, d_q, len(q)).tobytes() == got.tobytes(), k
+            one.release()
+        full = _expect_hits(_concat(segs, False)[0], q)["entry"]
+        nc = len(coll)
+        assert list(full[:nc]) == [50 if r == 700 else r for r in coll] and list(full[nc:nc + 7]) == wrap
+        assert list(full[nc + 7:nc + 11]) == [300, 50, 800, 3100]
+        assert (full[nc + 11:nc + 22] == nydus_gpu.MISS).all()
+        for h in (x2, x1, b):
+            h.release()
+
+
+# ---- 3: share, fork, isolation -----------------------------------------------------
+def _filler(rng, k, usize=0x10000):
+    r = np.zeros(k, rafs.CHUNK_INFO_DTYPE)
+    r["block_id"] = rng.integers(0, 256, (k, 32), dtype=np.uint8)
+    r["uncompressed_size"] = usize
+    r["index"] = rng.integers(0, 1 << 20, k)
+    r["uncompressed_offset"] = rng.integers(0, 1 << 30, k).astype(np.uint64) * 4096
+    r["compressed_offset"] = rng.integers(0, 1 << 40, k)
+    r["compressed_size"] = rng.integers(1, 1 << 16, k)
+    return r
+
+
+def _pack(eng, d, tar):
+    w = eng.pack(dict=d)
+    w.write(tar)
+    ch, out, st = w.close()
+    return ch, out, st
+
+
+@pytest.mark.parametrize("order", ["x2-first", "x1-first"])
+def test_share_fork_and_isolation(tars, oracle, order):
+    """b = create(R1); x1 = extend(b, R2) forks (capacities as the plan says);
+    x2 = extend(x1, R3) shares; x3 = extend(x1, R4), after x2 took the tip,
+    forks.  R3 holds digests absent from x1, equal to x1 rows, sharing bucket
+    and tag with x1 rows, and homed just before x1 rows' slots.  Every handle
+    answers probes and a Pack as the single-create dict of its own rows, before
+    and after the others are released in either order."""
+    from test_gpu_dict import _oracle_expect, _pack_records, _same
+    cs = 0x10000
+    rng = np.random.default_rng(31)
+    tar = tars["oci_lower"] + b""
+    eng = nydus_gpu.Engine(chunk_size=cs)
+    try:
+        real = _pack_records(eng, tars["chunk_dict"])  # shares files with oci_lower
+        assert len(real) >= 8
+        real["blob_index"] = 0
+        real = real[rng.permutation(len(real))]
+        qt = len(real) // 4
+        R1 = np.concatenate([_filler(rng, 1000 - qt), real[:qt]])
+        R2 = np.concatenate([real[qt:2 * qt], _filler(rng, 500 - qt)])
+        cap1, tcap1 = _fork_caps(1000, 500)
+        assert (cap1, tcap1) == (2250, 8192)
+        x1_rows = np.concatenate([R1, R2])
+        absent = _filler(rng, 200)
+        equal = np.concatenate([R1[5:25], R2[7:27], real[:2]]).copy()
+        equal["index"] += 7  # never the answer: base's rows win
+        sametag = _filler(rng, 40)
+        sametag["block_id"][:, :12] = x1_rows["block_id"][100:140, :12]
+        before = _filler(rng, 40)
+        slots = dc.home_slot(x1_rows["block_id"][200:240], tcap1 - 1)
+        for j in range(40):
+            w = _words_homed(rng, (int(slots[j]) - 1) % tcap1, tcap1 - 1, 1)[0]
+            before["block_id"][j, :8] = np.frombuffer(np.uint64(w).tobytes(), np.uint8)
+        R3 = np.concatenate([absent, equal, real[2 * qt:3 * qt], sametag, before])
+        R3 = R3[rng.permutation(len(R3))]
+        assert len(R3) <= cap1 - 1500
+        R4 = np.concatenate([_filler(rng, 100), real[3 * qt:]])
+        b = eng.dict_create(R1)
+        ib = b.info()
+        assert (ib["entries"], ib["record_capacity"], ib["table_capacity"], ib["shares_base_storage"]) == \
+            (1000, 1000, 2048, False)
+        x1 = b.extend(R2)
+        x2 = x1.extend(R3)
+        x3 = x1.extend(R4)
+        i1, i2, i3 = x1.info(), x2.info(), x3.info()
+        assert (i1["record_capacity"], i1["table_capacity"], i1["shares_base_storage"]) == (cap1, tcap1, False)
+        assert (i2["record_capacity"], i2["table_capacity"], i2["shares_base_storage"]) == (cap1, tcap1, True)
+        cap3, tcap3 = _fork_caps(1500, len(R4))
+        assert (i3["record_capacity"], i3["table_capacity"], i3["shares_base_storage"]) == (cap3, tcap3, False)
+        handles = {"b": (b, [R1]), "x1": (x1, [R1, R2]), "x2": (x2, [R1, R2, R3]), "x3": (x3, [R1, R2, R4])}
+        for name, (h, parts) in handles.items():
+            assert h.entries == h.info()["entries"] == sum(len(p) for p in parts), name
+        q = np.concatenate([R1["block_id"][::7], R2["block_id"], R3["block_id"], R4["block_id"],
+                            rng.integers(0, 256, (64, 32), dtype=np.uint8)])
+        d_q = _dev(q)
+        want = {}
+        for name, (h, parts) in handles.items():  # each handle's own concatenation, created in one go
+            rows, _ = _concat([(p, 1) for p in parts], False)
+            one = eng.dict_create(rows)
+            ch, out, st = _pack(eng, one, tar)
+            ech, dig, dec = _oracle_expect(oracle, tar, cs, "blake3", rows)
+            assert ch.tobytes() == ech.tobytes()
+            _same(out, dig, dec, name)
+            assert st["dict_chunks"] == int((dec["kind"] == 2).sum()) > 0
+            hits = _probe(one, d_q, len(q))
+            assert hits.tobytes() == _expect_hits(rows, q).tobytes(), name
+            want[name] = (hits.tobytes(), out.tobytes(), json.dumps(st, sort_keys=True, default=int))
+            one.release()
+        assert len({v[1] for v in want.values()}) >= 2  # the Packs do tell handles apart
+        # x1 still misses on every R3-only digest
+        r3_only = np.array([bytes(x) not in _first_rows(x1_rows["block_id"]) for x in R3["block_id"]])
+        o = len(R1["block_id"][::7]) + len(R2)
+        assert r3_only.sum() >= 280
+        assert (_probe(x1, d_q, len(q))["entry"][o:o + len(R3)][r3_only] == nydus_gpu.MISS).all()
+        assert (_probe(x2, d_q, len(q))["entry"][o:o + len(R3)][r3_only] != nydus_gpu.MISS).all()
+
+        def verify(alive):
+            for name in alive:
+                h = handles[name][0]
+                assert _probe(h, d_q, len(q)).tobytes() == want[name][0], name
+                ch, out, st = _pack(eng, h, tar)
+                assert out.tobytes() == want[name][1], name
+                assert json.dumps(st, sort_keys=True, default=int) == want[name][2], name
+
+        verify(["b", "x1", "x2", "x3"])
+        first, second = ("x2", "x1") if order == "x2-first" else ("x1", "x2")
+        handles[first][0].release()
+        verify([n for n in handles if n != first])
+        handles[second][0].release()
+        verify(["b", "x3"])
+        b.release()
+        verify(["x3"])
+        x3.release()
+    finally:
+        eng.close()
+
+
+# ---- 4: append under load -----------------------------------------------------------
+def test_append_under_load_and_racing_extends():
+    """One thread runs ~50 dedup calls against x1 on a stream (an lds1024 shape
+    and a grid shape) while another chains 32 in-place extends on top of x1 whose
+    rows are the very digests x1 misses: every result equals x1's, and the final
+    handle equals its concatenation.  Then two threads extend one base at once:
+    exactly one shares."""
+    import torch
+    cases = [dc.get("mixed", n, 4096, True) for n in (1025, 4097)]
+    eng = nydus_gpu.Engine(chunk_size=dc.CHUNK_SIZE)
+    rng = np.random.default_rng(77)
+    try:
+        dd, ds, db, di, duoff, nb = cases[1].dict
+        R1 = _recs(dd, ds, db, di, duoff)
+        R2 = _filler(rng, 2000)
+        b = eng.dict_create(R1)
+        x1 = b.extend(R2)
+        m1 = len(R1) + 2000
+        # the appended rows: chunk digests of both cases that x1 does not hold, then filler
+        have = _first_rows(np.concatenate([R1, R2])["block_id"])
+        fresh = [d for c in cases for d in c.digests if bytes(d) not in have]
+        fresh = np.stack(list({bytes(d): d for d in fresh}.values()))[:800]
+        assert len(fresh) == 800
+        ext = _filler(rng, 1600, dc.CHUNK_SIZE)
+        ext["block_id"][::2] = fresh
+        assert x1.info()["record_capacity"] >= m1 + 1600
+        eng.set_dict(x1)
+        work = []
+        for c in cases:
+            ch = np.zeros(c.n, nydus_gpu.CHUNK_DTYPE)
+            ch["length"] = c.lengths
+            ch["file_index"] = np.arange(c.n)
+            rec0 = np.zeros(c.n, nydus_gpu.RESULT_DTYPE)
+            rec0["digest"] = c.digests
+            rec0["kind"] = nydus_gpu.DIGESTED
+            d_ch = _dev(ch)
+            ref, _ = _dedup(eng, "one", c, d_ch, rec0)  # x1's answer, before any append
+            work.append((c, d_ch, rec0, ref.tobytes()))
+        outs, errs, tips = [], [], [x1]
+        stream = torch.cuda.Stream()
+
+        def prober():
+            try:
+                for i in range(50):
+                    c, d_ch, rec0, _ = work[i % 2]
+                    out = _dev(rec0)
+                    torch.cuda.current_stream().synchronize()  # the upload, before the side stream reads it
+                    eng.dedup_device(d_ch.data_ptr(), c.n, out.data_ptr(), stream=stream.cuda_stream)
+                    outs.append((i % 2, out))
+            except Exception as e:  # noqa: BLE001
+                errs.append(e)
+
+        def extender():
+            try:
+                for i in range(32):
+                    tips.append(tips[-1].extend(ext[50 * i:50 * i + 50]))
+            except Exception as e:  # noqa: BLE001
+                errs.append(e)
+
+        th = [threading.Thread(target=prober), threading.Thread(target=extender)]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+        torch.cuda.synchronize()
+        assert not errs, errs
+        eng.device_status()
+        assert len(outs) == 50 and len(tips) == 33
+        for k, out in outs:
+            assert out.cpu().numpy().tobytes() == work[k][3], "a dedup against x1 saw an append"
+        assert all(t.info()["shares_base_storage"] for t in tips[1:])
+        assert tips[-1].entries == m1 + 1600
+        pieces = [(ext[50 * i:50 * i + 50], 0) for i in range(32)]  # each extend brings one more blob
+        rows, _ = _concat([(R1, 0), (R2, 0)] + pieces, False)
+        one = eng.dict_create(rows)
+        for c, d_ch, rec0, ref in work:
+            res = []
+            for h in (tips[-1], one, x1):
+                eng.set_dict(h)
+                res.append(_dedup(eng, "one", c, d_ch, rec0))
+            assert res[0][0].tobytes() == res[1][0].tobytes() and res[0][1] == res[1][1]
+            assert res[2][0].tobytes() == ref
+            assert res[0][0].tobytes() != ref  # the appended digests do turn NEW chunks into DICT ones
+        q = np.concatenate([ext["block_id"], R1["block_id"], rng.integers(0, 256, (32, 32), dtype=np.uint8)])
+        d_q = _dev(q)
+        assert _probe(tips[-1], d_q, len(q)).tobytes() == _probe(one, d_q, len(q)).tobytes() == \
+            _expect_hits(rows, q).tobytes()
+        # a handle in the middle of the chain still ends where it ended
+        mid, _ = _concat([(R1, 0), (R2, 0)] + pieces[:16], False)
+        assert _probe(tips[16], d_q, len(q)).tobytes() == _expect_hits(mid, q).tobytes()
+        eng.set_dict(None)
+        one.release()
+        # two threads extending one base at once: one appends in place, one copies
+        base = tips[-1]
+        add = [_filler(rng, 40), _filler(rng, 40)]
+        got, bar = [None, None], threading.Barrier(2)
+
+        def race(i):
+            try:
+                bar.wait()
+                got[i] = base.extend(add[i])
+            except Exception as e:  # noqa: BLE001
+                errs.append(e)
+
+        th = [threading.Thread(target=race, args=(i,)) for i in range(2)]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+        assert not errs, errs
+        assert sorted(g.info()["shares_base_storage"] for g in got) == [False, True]
+        for g, a in zip(got, add):
+            r2, _ = _concat([(rows, 0), (a, 0)], False)
+            q2 = np.concatenate([add[0]["block_id"], add[1]["block_id"], q[:200]])
+            assert _probe(g, _dev(q2), len(q2)).tobytes() == _expect_hits(r2, q2).tobytes()
+        for h in got + tips + [b]:
+            h.release()
+    finally:
+        eng.close()
+
+
+# ---- 5: bootstrap and Pack flow ---------------------------------------------------------
+def _write_boot(path, recs, cs, ids, digester="blake3"):
+    blobs = rafs.make_blob_table(ids, cs, digester=digester)
+    flags = (FLAG_SHA256 if digester == "sha256" else FLAG_BLAKE3) | 0x1
+    with open(path, "wb") as f:
+        f.write(rafs.write_v6_bootstrap(recs, cs, flags=flags, blobs=blobs))
+    return blobs
+
+
+def test_fold_packed_layers_into_a_dict(tars, oracle, tmp_path):
+    """Pack A with no dict, extend an empty dict with A's chunk table, Pack B
+    against it == the oracle with A's records; the same through
+    extend_bootstrap, then a third layer on top.  Incompatible bootstraps are
+    refused and the base stays usable; the blob-table rule is enforced."""
+    from test_gpu_dict import _oracle_expect, _pack_records, _same
+    cs = 0x10000
+    A, B, C = tars["chunk_dict"], tars["oci_lower"] + b"", tars["oci_upper"]
+    eng = nydus_gpu.Engine(chunk_size=cs)
+    try:
+        ra, rc = _pack_records(eng, A), _pack_records(eng, C)
+        assert (ra["blob_index"] == 0).all() and (rc["blob_index"] == 0).all()
+        ech, dig, dec = _oracle_expect(oracle, B, cs, "blake3", ra)
+        empty = eng.dict_create(np.zeros(0, rafs.CHUNK_INFO_DTYPE))
+        assert empty.entries == 0 and empty.info()["blobs"] == 0
+        da = empty.extend(ra)
+        assert da.entries == len(ra) and da.info()["blobs"] == 1
+        ch, out, st = _pack(eng, da, B)
+        assert ch.tobytes() == ech.tobytes()
+        _same(out, dig, dec, "extend(empty, A)")
+        assert st["dict_chunks"] == int((dec["kind"] == 2).sum()) > 0
+        same = da.extend(np.zeros(0, rafs.CHUNK_INFO_DTYPE))  # n == 0: equal to its base
+        assert same.entries == da.entries and same.info()["blobs"] == 1
+        assert _pack(eng, same, B)[1].tobytes() == out.tobytes()
+        same.release()
+        # through bootstrap files
+        pa, pc = str(tmp_path / "a.boot"), str(tmp_path / "c.boot")
+        _write_boot(pa, ra, cs, ["aa" * 32])
+        _write_boot(pc, rc, cs, ["cc" * 32])
+        fa = empty.extend_bootstrap(pa)
+        assert _pack(eng, fa, B)[1].tobytes() == out.tobytes()
+        fac = fa.extend_bootstrap(pc)
+        rows, nb = _concat([(ra, 1), (rc, 1)], True)
+        assert fac.entries == len(rows) and fac.info()["blobs"] == nb == 2
+        ech, dig, dec2 = _oracle_expect(oracle, B, cs, "blake3", rows)
+        ch, out2, st = _pack(eng, fac, B)
+        _same(out2, dig, dec2, "A then C")
+        one = eng.dict_open(pa).extend_bootstrap(pc)  # an opened dict as the base
+        assert _pack(eng, one, B)[1].tobytes() == out2.tobytes()
+        one.release()
+        # refused bootstraps; the base stays usable
+        ps, pk = str(tmp_path / "sha.boot"), str(tmp_path / "cs.boot")
+        _write_boot(ps, rc, cs, ["cc" * 32], digester="sha256")
+        _write_boot(pk, rc, 2 * cs, ["cc" * 32])
+        for p in (ps, pk):
+            with pytest.raises(nydus_gpu.NgpuError) as x:
+                fa.extend_bootstrap(p)
+            assert x.value.code == nydus_gpu.EINVAL, p
+        with pytest.raises(nydus_gpu.NgpuError) as x:
+            fa.extend_bootstrap(str(tmp_path / "missing"))
+        assert x.value.code == nydus_gpu.EIO
+        assert fa.entries == len(ra) and _pack(eng, fa, B)[1].tobytes() == out.tobytes()
+        # the blob-table rule: exactly one side with a table is refused
+        tbl = rafs.make_blob_table(["cc" * 32], cs)
+        for base, blobs in ((fa, None), (da, tbl)):
+            with pytest.raises(nydus_gpu.NgpuError) as x:
+                base.extend(rc, blobs)
+            assert x.value.code == nydus_gpu.EINVAL
+        bad = rc.copy()
+        bad["blob_index"][len(bad) // 2] = 1
+        with pytest.raises(nydus_gpu.NgpuError) as x:
+            fa.extend(bad, tbl)  # blob 1 of a 1-blob table
+        assert x.value.code == nydus_gpu.EFORMAT
+        with nydus_gpu.Engine(chunk_size=cs, digester="sha256") as other:  # an engine the base does not fit
+            with _borrowed(fa, other) as v, pytest.raises(nydus_gpu.NgpuError) as x:
+                v.extend(rc, tbl)
+            assert x.value.code == nydus_gpu.EINVAL
+        assert _pack(eng, da, B)[1].tobytes() == out.tobytes()
+        for h in (fac, fa, da, empty):
+            h.release()
+    finally:
+        eng.close()
+
+
+DICT_ID, OTHER_ID = "ab" * 32, "cd" * 32
+
+
+@pytest.fixture(scope="module")
+def check_case(oracle, tars, tmp_path_factory):
+    """oci_lower packed against the chunk_dict bootstrap (its DICT records name
+    blob DICT_ID), and a second bootstrap of rows nobody references."""
+    from test_blob import cpu_stream
+    cs = 0x100000
+    with nydus_gpu.Engine(chunk_size=cs) as eng:
+        ch, out, _ = eng.pack_tar(tars["chunk_dict"])
+        tab = nydus_gpu.chunk_table(ch, out).view(rafs.CHUNK_INFO_DTYPE).reshape(-1)
+    blobs = rafs.make_blob_table([DICT_ID], cs, counts=[len(tab)])
+    boot = rafs.write_v6_bootstrap(tab, cs, flags=0x5, blobs=blobs)
+    d = tmp_path_factory.mktemp("extend-check")
+    other = _filler(np.random.default_rng(5), 300, cs)
+    (d / "b.boot").write_bytes(boot)
+    (d / "a.boot").write_bytes(rafs.write_v6_bootstrap(other, cs, flags=0x5,
+                                                       blobs=rafs.make_blob_table([OTHER_ID], cs, counts=[300])))
+    stream = cpu_stream(oracle, tars["oci_lower"], cs, "none", dict_boot=boot)[0]
+    (d / "stream").write_bytes(stream)
+    v6 = rafs.read_v6(nydus_gpu.unpack_entry(stream, "image.boot")[0])
+    nd = sum(v6["blob_ids"][int(x)] == DICT_ID for x in v6["chunks"]["blob_index"])
+    assert nd > 0
+    return {"cs": cs, "dir": d, "stream": stream, "tab": tab, "blobs": blobs, "other": other, "nd": nd}
+
+
+def test_check_resolves_records_in_the_extension(check_case):
+    """Engine.check of a stream whose DICT records point into the extension:
+    resolved, their blob ids coming from the appended blob table; against the
+    base alone the same records are DICT-bad."""
+    c = check_case
+    with nydus_gpu.Engine(chunk_size=c["cs"]) as eng:
+        base = eng.dict_create(c["other"], rafs.make_blob_table([OTHER_ID], c["cs"]))
+        x = base.extend(c["tab"], c["blobs"])
+        rep = eng.check(c["stream"], dict=x)
+        assert (rep["dict_checked"], rep["dict_bad"], rep["skipped"], rep["bad"]) == (c["nd"], 0, 0, 0), rep
+        rep = eng.check(c["stream"], dict=base)
+        assert (rep["dict_checked"], rep["dict_bad"], rep["bad"]) == (c["nd"], c["nd"], c["nd"]), rep
+        y = eng.dict_open(str(c["dir"] / "a.boot")).extend_bootstrap(str(c["dir"] / "b.boot"))
+        rep = eng.check(c["stream"], dict=y)
+        assert (rep["dict_checked"], rep["dict_bad"], rep["bad"]) == (c["nd"], 0, 0), rep
+        for h in (y, x, base):
+            h.release()
+
+
+# ---- 6: node dicts ---------------------------------------------------------------------
+COPY = nydus_gpu.NODE_DICT_PARTITION | nydus_gpu.NODE_EXCHANGE_COPY
+ROUTED = nydus_gpu.NODE_DICT_PARTITION | nydus_gpu.NODE_EXCHANGE_ROUTED
+
+
+@pytest.mark.parametrize("W,mode", [(W, m) for W in (2, 4) for m in (COPY, ROUTED, nydus_gpu.NODE_DICT_REPLICATE)],
+                         ids=[f"W{W}-{n}" for W in (2, 4) for n in ("copy", "routed", "replicate")])
+def test_node_dict_extend(tars, oracle, W, mode):
+    """Node.dict_extend twice (the second in place) on a W-part node: streaming
+    Packs over the node equal the oracle with the concatenated dict and the
+    same Packs against a node dict created in one go."""
+    from test_gpu_dict import _oracle_expect, _pack_records, _same
+    cs = 0x10000
+    rng = np.random.default_rng(60 + W)
+    names = ["oci_lower", "oci_upper", "alpine_like", "oci_lower"][:max(W, 3)]
+    with nydus_gpu.Engine(chunk_size=cs) as eng:
+        real = np.concatenate([_pack_records(eng, tars[n]) for n in ("chunk_dict", "oci_upper")])
+    real["blob_index"] = 0
+    real = real[rng.permutation(len(real))]
+    t = len(real) // 3
+    segs = [(np.concatenate([_filler(rng, 3000), real[:t]]), 2),
+            (np.concatenate([real[t:2 * t], _filler(rng, 1500)]), 1),
+            (np.concatenate([_filler(rng, 200), real[2 * t:]]), 3)]
+    segs[0][0]["blob_index"][:100] = 1
+    segs[2][0]["blob_index"][::3] = 2
+    tables = [rafs.make_blob_table([f"{s}{i:063x}" for i in range(nb)], cs) for s, (_, nb) in enumerate(segs)]
+    rows, total = _concat(segs, True)
+    assert total == 6
+    node = nydus_gpu.Node([0] * W, chunk_size=cs)
+    try:
+        d0 = node.dict_create(segs[0][0], tables[0], mode=mode)
+        d1 = node.dict_extend(d0, segs[1][0], tables[1])
+        d2 = node.dict_extend(d1, segs[2][0], tables[2])
+        one = node.dict_create(rows, np.concatenate(tables), mode=mode)
+        assert (d0.entries, d1.entries, d2.entries) == (len(segs[0][0]), len(segs[0][0]) + len(segs[1][0]), len(rows))
+        assert not d1.info()["shares_base_storage"] and d2.info()["shares_base_storage"]
+        assert d2.info()["blobs"] == one.info()["blobs"] == 6
+        with _borrowed(d2, node.engines[0]) as v, pytest.raises(nydus_gpu.NgpuError) as x:
+            v.extend(segs[1][0], tables[1])  # a node dict is not for the engine call
+        assert x.value.code == nydus_gpu.EINVAL
+        res = {}
+        for label, d, parts in (("d2", d2, 3), ("one", one, 3), ("d1", d1, 2), ("d0", d0, 1)):
+            ws = [node.pack(d) for _ in names]
+            for w, n in zip(ws, names):
+                w.write(tars[n])
+            res[label] = [w.close() for w in ws]
+            if label != "one":
+                part, _ = _concat(segs[:parts], True)
+                for (ch, out, st), n in zip(res[label], names):
+                    ech, dig, dec = _oracle_expect(oracle, tars[n], cs, "blake3", part)
+                    assert ch.tobytes() == ech.tobytes()
+                    _same(out, dig, dec, (label, n))
+                    assert st["dict_chunks"] == int((dec["kind"] == 2).sum())
+        for (_, a, sa), (_, b, sb) in zip(res["d2"], res["one"]):
+            assert a.tobytes() == b.tobytes() and sa == sb
+        assert sum(st["dict_chunks"] for _, _, st in res["d2"]) > sum(st["dict_chunks"] for _, _, st in res["d0"])
+        with nydus_gpu.Engine(chunk_size=cs) as eng:  # a plain dict is not for the node call
+            plain = eng.dict_create(segs[1][0], tables[1])
+            with pytest.raises(nydus_gpu.NgpuError) as x:
+                node.dict_extend(plain, segs[1][0], tables[1])
+            assert x.value.code == nydus_gpu.EINVAL
+            plain.release()
+        for h in (one, d2, d1, d0):
+            h.release()
+    finally:
+        node.close()
+
+
+# ---- 7: CLI -----------------------------------------------------------------------------
+def test_inspect_check_folds_several_dicts(check_case):
+    """inspect --check STREAM --dict A --dict B exits 0 where --dict A alone
+    reports the B-resident DICT records as unresolved."""
+    c = check_case
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "nydus-snapshotter_amd")] +
+                                        [p for p in [env.get("PYTHONPATH")] if p])
+
+    def run(*dicts):
+        args = [a for p in dicts for a in ("--dict", str(c["dir"] / p))]
+        return subprocess.run([sys.executable, "-m", "nydus_gpu.inspect", "--check", str(c["dir"] / "stream"),
+                               *args], capture_output=True, text=True, timeout=120, env=env)
+    r = run("a.boot")
+    assert r.returncode == 1, r.stdout + r.stderr
+    rep = json.loads(r.stdout)
+    assert rep["dict_bad"] == rep["bad"] == c["nd"]
+    r = run("a.boot", "b.boot")
+    assert r.returncode == 0, r.stdout + r.stderr
+    rep = json.loads(r.stdout)
+    assert (rep["dict_checked"], rep["dict_bad"], rep["bad"]) == (c["nd"], 0, 0)
