@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dict_hash.hpp"
 #include "nydus_gpu.h"
 
 namespace ngpu {
@@ -64,19 +65,8 @@ __device__ __forceinline__ uint32_t rotr32(uint32_t x, uint32_t n) {
   return __builtin_amdgcn_alignbit(x, x, n);
 }
 
-// 64-bit hash-table slot: tag (digest word 2) in the high half, id in the low.
-// Equal digests give equal tags, so an atomic min over a slot keeps the
-// smallest id ("first in stream / table order wins").  Word 2 == 0xFFFFFFFF
-// is stored as 0xFFFFFFFE so that no slot equals kEmpty: two digests that
-// differ only in that word then share a tag and are told apart by the full
-// compare (the tagff case of tests/dedup_cases.py).
-__device__ __forceinline__ uint32_t digest_tag(const uint32_t *w) {
-  uint32_t t = w[2];
-  return t == 0xFFFFFFFFu ? 0xFFFFFFFEu : t;
-}
-__device__ __forceinline__ uint64_t digest_bucket(const uint32_t *w) {
-  return ((uint64_t)w[1] << 32 | w[0]) * 0x9E3779B97F4A7C15ull;
-}
+// digest_tag, digest_bucket and owner_of (the hash-table slot's tag, the home
+// slot and the node owner of a digest): dict_hash.hpp, shared with host code.
 
 // ---- single-pass scan across workgroups (decoupled look-back) -------------
 // A workgroup takes a ticket (its tile, in dispatch order), scans its 256

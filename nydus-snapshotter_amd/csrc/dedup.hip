@@ -20,7 +20,8 @@
 // tag remap, wrapping probe chains, one hot slot, offsets past 2^32.
 //
 // Hash table: open addressing, linear probing over 8-byte slots
-// {tag = digest word 2 : id}; bucket = (digest words 0,1) * golden ratio.
+// {tag = digest word 2 : id}; bucket = (digest words 0,1) * golden ratio,
+// folded once (dict_hash.hpp).
 // Roofline: HBM-bound probes.
 #include <stddef.h>
 #include <stdlib.h>
@@ -1404,11 +1405,6 @@ void launch_dict_probe(const uint8_t *digests, uint64_t stride, uint64_t n,
 
 // ---- node dict exchange (node.hip) -------------------------------------------
 namespace {
-
-__device__ __forceinline__ uint32_t owner_of(uint32_t w0, uint32_t W) {
-  const uint32_t hi = (w0 & 0xFF) << 8 | ((w0 >> 8) & 0xFF);  // digest bytes 0, 1
-  return (uint32_t)(((uint64_t)hi * W) >> 16);
-}
 
 __global__ void pack_digests(const uint8_t *__restrict__ src, uint64_t stride, uint64_t n,
                              uint8_t *__restrict__ dst) {

@@ -78,10 +78,6 @@ struct ngpu_node {
 
 namespace ngpu {
 
-static uint32_t owner_of(const uint8_t *d, uint32_t W) {
-  return (uint32_t)((((uint64_t)d[0] << 8 | d[1]) * W) >> 16);
-}
-
 static void free_io(ngpu_dict::PartIO &io, int device) {
   DeviceGuard g(device);
   if (io.stream) (void)hipStreamSynchronize(io.stream);

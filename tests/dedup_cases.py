@@ -7,9 +7,10 @@ GPU library.  The dedup stage never looks at a chunk's bytes, only at its
 (plus the chunk dict's rows) and reaches the kernels through records marked
 NGPU_DIGESTED -- no byte is hashed.
 
-A digest as csrc/common.hpp reads it:
+A digest as csrc/dict_hash.hpp reads it:
   bytes 0-7    the bucket words (digest_bucket: their u64 times the golden
-               ratio, masked to the table size, is the home slot)
+               ratio, folded once and masked to the table size, is the home
+               slot: home_slot below, tied to the header by test_dict_hash.py)
   bytes 8-11   the tag (digest_tag: word 2, 0xFFFFFFFF stored as 0xFFFFFFFE)
   bytes 12-31  the tail: bytes 12-15 a group word (equal inside a tagchain
                group, so bytes 8-15 -- the key of oracle/dedup_ref.c's own
@@ -37,7 +38,7 @@ of the layered dict is out of scope: no case has a zero-length chunk.
 """
 import numpy as np
 
-GOLDEN = 0x9E3779B97F4A7C15  # digest_bucket's multiplier (common.hpp)
+GOLDEN = 0x9E3779B97F4A7C15  # digest_bucket's multiplier (dict_hash.hpp)
 CHUNK_SIZE = 0x1000000       # the engine's chunk size in these tests: 16 MiB
 S1, S2 = CHUNK_SIZE, CHUNK_SIZE - 4095
 EDGE_LENGTHS = (1, 4095, 4096, 4097)
@@ -54,10 +55,31 @@ def lds_mask(n):
     return mask
 
 
+def word_slot(words, mask):
+    """Home slot of u64 bucket words: the product folded once (x ^ x >> 32),
+    masked.  The one Python statement of digest_bucket; test_dict_hash.py ties
+    it to the header."""
+    x = np.multiply(np.asarray(words, np.uint64), np.uint64(GOLDEN))
+    return (x ^ (x >> np.uint64(32))) & np.uint64(mask)
+
+
 def home_slot(digests, mask):
     """digest_bucket(d) & mask for an (n, 32) u8 array."""
-    w = np.ascontiguousarray(digests[:, :8]).view("<u8")[:, 0]
-    return np.multiply(w, np.uint64(GOLDEN)) & np.uint64(mask)
+    return word_slot(np.ascontiguousarray(digests[:, :8]).view("<u8")[:, 0], mask)
+
+
+def tag_of(digests):
+    """digest_tag(d) for an (n, 32) u8 array: word 2, 0xFFFFFFFF as 0xFFFFFFFE."""
+    t = np.ascontiguousarray(digests[:, 8:12]).view("<u4")[:, 0].copy()
+    t[t == 0xFFFFFFFF] = 0xFFFFFFFE
+    return t
+
+
+def owner_of(digests, W):
+    """The node owner of each digest of an (n, 32) u8 array (dist.owner_of's
+    rule; test_dict_hash.py holds the statements together)."""
+    hi = digests[:, 0].astype(np.int64) << 8 | digests[:, 1].astype(np.int64)
+    return (hi * W) >> 16
 
 
 def lds_thread_wave(n, c):
@@ -121,12 +143,12 @@ class _Builder:
         return int(self.rng.integers(0, np.iinfo(np.uint64).max, dtype=np.uint64, endpoint=True))
 
     def words_for_slot(self, slot, mask, count):
-        """Brute force over the multiply: `count` distinct bucket words whose
+        """Brute force over home_slot: `count` distinct bucket words whose
         home slot in a table of mask + 1 slots is `slot`."""
         found = []
         while len(found) < count:
             w = self.rng.integers(0, np.iinfo(np.uint64).max, 1 << 18, dtype=np.uint64, endpoint=True)
-            hit = w[(np.multiply(w, np.uint64(GOLDEN)) & np.uint64(mask)) == np.uint64(slot)]
+            hit = w[home_slot(w.view(np.uint8).reshape(-1, 8), mask) == np.uint64(slot)]
             found.extend(int(x) for x in hit)
         found = list(dict.fromkeys(found))[:count]
         assert len(found) == count

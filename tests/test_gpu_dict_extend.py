@@ -275,7 +275,7 @@ def _words_homed(rng, slot, mask, count):
     found = []
     while len(found) < count:
         w = rng.integers(0, np.iinfo(np.uint64).max, 1 << 18, dtype=np.uint64, endpoint=True)
-        found.extend(int(x) for x in w[(np.multiply(w, np.uint64(dc.GOLDEN)) & np.uint64(mask)) == np.uint64(slot)])
+        found.extend(int(x) for x in w[dc.home_slot(w.view(np.uint8).reshape(-1, 8), mask) == np.uint64(slot)])
     return list(dict.fromkeys(found))[:count]
 
 
