@@ -296,11 +296,60 @@ int ngpu_dict_extend(ngpu_engine *eng, ngpu_dict *base, const void *records, uin
  * ngpu_dict_open's compatibility checks (digester flag, chunk size, FsVersion 6). */
 int ngpu_dict_extend_bootstrap(ngpu_engine *eng, ngpu_dict *base, const char *path,
                                uint32_t flags, ngpu_dict **out);
+/* ---- dict retire: drop the records of deleted blobs from a dict ----
+ * out = base without the records of the listed inner blobs (blobs[0, n), any
+ * order, duplicates allowed).  Equal, for every probe, Pack, Check, stats field
+ * and export, to ngpu_dict_create over a filtered copy of base:
+ *   the records of base, in table order, whose blob_index is not listed, each
+ *   with blob_index replaced by its rank among the kept blobs;
+ *   the blob table rows of the kept blobs, in order.  A base with only a blob
+ *   count gives out only the new count: blobs(base) - distinct listed blobs.
+ * Entry ids are positions among the survivors.  First table entry still wins:
+ * when the winning row of a digest leaves, the next surviving row with that
+ * digest wins.  out keeps compressed placements iff base did.  Only the handle's
+ * own entries(base) records count: rows a later in-place extend appended to the
+ * same storage are not seen.  base is not modified and not released; out carries
+ * one reference.  flags must be 0.
+ *
+ * out always sits on a storage of its own (nothing a live handle can see is
+ * written, so probes of base may run meanwhile on other streams and threads),
+ * sized like the copy of an extend that adds nothing: s + s / 2 record slots
+ * for s survivors and the table ngpu_dict_create gives for that many, so that
+ * the next extends of out, up to s / 2 records in all, append in place.  n == 0
+ * is a compacting copy equal to base (the way to drop the id ranges a failed
+ * extend or an abandoned tip left dead on a storage).  Retiring every blob gives
+ * a valid dict of 0 entries and 0 blobs: it dedups nothing and can be extended.
+ * The device work (keep bits, their scan, the compaction, the table build) runs
+ * on a stream of the library's own, outside the engine lock, and is complete
+ * when the call returns.
+ *
+ * Rejected before any GPU work, with *out = NULL: base == NULL, flags != 0 or
+ * n && !blobs (NGPU_EINVAL); an index >= blobs(base) (NGPU_EINVAL); a node dict
+ * (NGPU_EINVAL: ngpu_node_dict_retire).  On failure base is untouched. */
+int ngpu_dict_retire(ngpu_engine *eng, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                     uint32_t flags, ngpu_dict **out);
+/* The handle's rows back out of HBM: entries(d) 80-B RAFS v6 chunk-info records in
+ * table order and its 256-B blob records, such that ngpu_dict_create over them
+ * answers as d does.  block_id, blob_index, uncompressed_size, uncompressed_offset
+ * and index come from the HBM rows; compressed_offset, compressed_size and flags
+ * from the placement rows (a dict without them: compressed_size =
+ * uncompressed_size, offset 0, flags 0, as ngpu_dict_load documents); file_offset
+ * and the reserved word are 0.  *n_records = entries(d) and *n_blobs = blobs(d) are
+ * always set.  records == NULL && cap == 0 only counts; cap < entries(d) is
+ * NGPU_EINVAL and nothing is written.  The blob table is written when blob_table
+ * is given and the handle has one (ngpu_dict_info.has_blob_table; blob_cap rows
+ * of room, too few: NGPU_EINVAL, nothing written).  Plain dicts and replicated
+ * node dicts (part 0's rows, the node handle's placements); a partitioned node
+ * dict returns NGPU_EUNSUPP. */
+int ngpu_dict_export(ngpu_engine *eng, const ngpu_dict *d, void *records, uint64_t cap,
+                     uint64_t *n_records, void *blob_table, uint32_t blob_cap, uint32_t *n_blobs);
 typedef struct {
   uint64_t entries, blobs;
   uint64_t record_capacity, table_capacity; /* of the storage it sits on (node dict: part 0) */
   uint32_t shares_base_storage;             /* 1: made by an in-place extend */
-  uint32_t reserved[3];
+  uint32_t has_blob_table;                  /* 1: it holds 256-B blob records (a reserved,
+                                               zero word until dict retire; still ABI 7) */
+  uint32_t reserved[2];
 } ngpu_dict_info;
 int ngpu_dict_info_get(const ngpu_dict *d, ngpu_dict_info *out);
 void ngpu_dict_retain(ngpu_dict *d);
@@ -571,6 +620,14 @@ int ngpu_node_dict_open(ngpu_node *node, const char *path, uint32_t mode, ngpu_d
  * in place or copies by its own fill.  A plain dict here is NGPU_EINVAL. */
 int ngpu_node_dict_extend(ngpu_node *node, ngpu_dict *base, const void *records, uint64_t n,
                           const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
+/* ngpu_dict_retire for node dicts.  A replicated dict retires every replica
+ * with the same result (global id = position) and the node handle's placement
+ * rows follow.  A partitioned dict returns NGPU_EUNSUPP: its parts' new global
+ * ids are ranks across all parts, which this call does not compute yet.  A
+ * plain dict here is NGPU_EINVAL.  *out is NULL on every failure and base stays
+ * usable. */
+int ngpu_node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                          uint32_t flags, ngpu_dict **out);
 int ngpu_node_dict_create(ngpu_node *node, const void *records, uint64_t n,
                           const void *blob_table, uint32_t n_blobs, uint32_t mode,
                           ngpu_dict **out);

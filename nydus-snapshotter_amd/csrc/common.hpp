@@ -293,6 +293,20 @@ void launch_dict_unpack(const uint8_t *recs, uint64_t n, const uint32_t *gids, u
 void launch_dict_pack(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,
                       const uint32_t *index, const uint64_t *uoff, const uint32_t *gid, uint64_t n,
                       DictRec *out, hipStream_t s);
+// dict_retire.hip (dict retire).  Launches 1-2: keep word and survivor count
+// per 64 records of rec[0, m) (a record stays unless bit rec.blob of bitmap is
+// set), then cnt -> exclusive prefixes in place.  words / cnt: (m + 63) / 64
+// entries; sums: dict_retire_scan_tiles(m) + 1 words, the last one receives the
+// number of survivors.  One scan tile is kRetireScanTile keep words.
+constexpr uint64_t kRetireScanTile = kTileThreads;  // words: 16,384 records
+uint64_t dict_retire_scan_tiles(uint64_t m);
+void launch_dict_keep_scan(const DictRec *rec, uint64_t m, const uint32_t *bitmap, uint32_t n_blobs,
+                           uint64_t *words, uint32_t *cnt, uint64_t *sums, hipStream_t s);
+// Launch 3: the survivors to out[0, n_out) in order, blob = remap[blob], gid =
+// the new position (prefix: launch 2's cnt).
+void launch_dict_compact(const DictRec *rec, uint64_t m, const uint64_t *words,
+                         const uint32_t *prefix, const uint32_t *remap, uint32_t n_blobs,
+                         DictRec *out, uint64_t n_out, hipStream_t s);
 
 // Device workspace, grown on demand and owned by the engine.
 struct Workspace {

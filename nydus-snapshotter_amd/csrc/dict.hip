@@ -30,7 +30,9 @@
 
 #include "blob.hpp"
 #include "dict_grow_plan.hpp"
+#include "dict_retire_plan.hpp"
 #include "engine_internal.hpp"
+#include "host_window.hpp"
 
 using namespace ngpu;
 
@@ -496,6 +498,180 @@ int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint
   return 0;
 }
 
+// ---- dict retire ---------------------------------------------------------------
+// The reverse of an extend: a new handle of base's records without those of the
+// listed blobs, as a dict created from the surviving rows would be.  Nothing of
+// base's storage is written (a probe of base on another stream reads what it
+// always read), so the result always sits on a storage of its own, with the
+// room a fork leaves (dict_retire_plan.hpp): launches 1-2 (dict_retire.hip) give
+// every record a keep bit and every 64 records the number of survivors before
+// them, the host reads the total and allocates, launch 3 moves the survivors,
+// launch 4 is the table build every dict gets.  The placement rows are compacted
+// on the host by the same keep words and prefixes, on the host pipelines' thread
+// pool (host_window.hpp), while launches 3-4 run: one thread's walk over 200M
+// bits, with the page faults of 3 GB of fresh rows, took 0.7 s against 19 ms on
+// the device (DESIGN.md §3 "Dict retire").
+
+void dict_retire_place(const DictKeep &keep, uint64_t m, const DictPlace *src, DictPlace *dst,
+                       uint64_t s) {
+  const uint64_t nw = (m + 63) / 64;
+  const uint64_t pieces = (nw + kRetireHostPiece - 1) / kRetireHostPiece;
+  const uint64_t *words = keep.words.data();
+  const uint32_t *prefix = keep.prefix.data();
+  run_indexed(host_threads(0), pieces, [=](uint64_t q) {
+    dict_retire_compact_rows(words, prefix, q * kRetireHostPiece,
+                             std::min(nw, (q + 1) * kRetireHostPiece), m, src, dst, s);
+  });
+}
+
+std::vector<uint8_t> dict_retire_blob_table(const std::vector<uint8_t> &table,
+                                            const std::vector<uint32_t> &remap) {
+  std::vector<uint8_t> t;
+  if (table.empty()) return t;
+  for (size_t b = 0; b < remap.size() && 256 * (b + 1) <= table.size(); ++b)
+    if (remap[b] != kRetiredBlob) t.insert(t.end(), table.begin() + 256 * b, table.begin() + 256 * (b + 1));
+  return t;
+}
+
+int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector<uint32_t> &bitmap,
+                        const std::vector<uint32_t> &remap, uint32_t nb, const DictPlace *place,
+                        DictKeep *keep, ngpu_dict **out) {
+  DeviceGuard dg(e->device);
+  const uint64_t m = base->dev.m;
+  const uint32_t nb0 = base->dev.n_blobs;
+  const uint64_t nw = (m + 63) / 64, nt = dict_retire_scan_tiles(m);
+  BuildStream bs(e->device);
+  if (!bs.s) return fail(e, NGPU_EHIP, "chunk dict: no build stream");
+  // one scratch allocation: keep words, tile sums (+ the total), word counts /
+  // prefixes, the retire bitmap and the blob remap
+  const uint64_t o_sums = 8 * nw, o_cnt = o_sums + 8 * (nt + 1), o_bits = o_cnt + 4 * nw,
+                 o_remap = o_bits + 4 * bitmap.size(), bytes = o_remap + 4 * remap.size();
+  uint8_t *scr = nullptr;
+  if (hipMalloc((void **)&scr, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(e, NGPU_ENOMEM, "dict retire: scratch allocation failed");
+  }
+  uint64_t *d_words = (uint64_t *)scr, *d_sums = (uint64_t *)(scr + o_sums);
+  uint32_t *d_cnt = (uint32_t *)(scr + o_cnt), *d_bits = (uint32_t *)(scr + o_bits),
+           *d_remap = (uint32_t *)(scr + o_remap);
+  // NGPU_DICT_TRACE=1: one stderr line per retire with its device time, launches
+  // 1-2 plus launches 3-4 (the allocation between them is host time)
+  static const bool trace = [] {
+    const char *v = getenv("NGPU_DICT_TRACE");
+    return v && v[0] == '1';
+  }();
+  hipEvent_t tev[4] = {};
+  bool timed = trace;
+  if (trace)
+    for (hipEvent_t &x : tev)
+      if (hipEventCreate(&x) != hipSuccess) x = nullptr, timed = false;
+  int rc = 0;
+  DictStorage *dst = nullptr;
+  DictKeep own_keep;
+  DictKeep &hk = keep ? *keep : own_keep;
+  uint64_t s = 0;
+  if (hipMemcpyAsync(d_bits, bitmap.data(), 4 * bitmap.size(), hipMemcpyHostToDevice, bs.s) != hipSuccess ||
+      (!remap.empty() && hipMemcpyAsync(d_remap, remap.data(), 4 * remap.size(),
+                                        hipMemcpyHostToDevice, bs.s) != hipSuccess))
+    rc = fail(e, NGPU_EHIP, "dict retire: upload failed");
+  if (!rc) {
+    if (timed) (void)hipEventRecord(tev[0], bs.s);
+    launch_dict_keep_scan(base->st ? base->st->rec : nullptr, m, d_bits, nb0, d_words, d_cnt, d_sums,
+                          bs.s);
+    if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict retire: keep scan failed");
+    if (timed) (void)hipEventRecord(tev[1], bs.s);
+  }
+  if (!rc && (place || keep) && nw) {
+    hk.words.resize(nw);
+    hk.prefix.resize(nw);
+    if (hipMemcpyAsync(hk.words.data(), d_words, 8 * nw, hipMemcpyDeviceToHost, bs.s) != hipSuccess ||
+        hipMemcpyAsync(hk.prefix.data(), d_cnt, 4 * nw, hipMemcpyDeviceToHost, bs.s) != hipSuccess)
+      rc = fail(e, NGPU_EHIP, "dict retire: keep words did not come back");
+  }
+  if (!rc && (hipMemcpyAsync(&s, d_sums + nt, 8, hipMemcpyDeviceToHost, bs.s) != hipSuccess ||
+              hipStreamSynchronize(bs.s) != hipSuccess))
+    rc = fail(e, NGPU_EHIP, "dict retire: keep scan failed");
+  if (!rc && s > m) rc = fail(e, NGPU_EHIP, "dict retire: %llu survivors of %llu records",
+                              (unsigned long long)s, (unsigned long long)m);
+  if (!rc)
+    rc = storage_alloc(e, dict_retire_rec_cap(s), dict_retire_table_cap(s), place && s, &dst);
+  if (!rc) {
+    dst->used = s;
+    if (timed) (void)hipEventRecord(tev[2], bs.s);
+    launch_dict_compact(base->st ? base->st->rec : nullptr, m, d_words, d_cnt, d_remap, nb0, dst->rec,
+                        s, bs.s);
+    launch_dict_build(dst->rec, s, dst->table, dst->table_cap, bs.s);
+    if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict retire: compaction failed");
+    if (timed) (void)hipEventRecord(tev[3], bs.s);
+  }
+  // the placement rows, while the device moves the records
+  if (!rc && place && s) dict_retire_place(hk, m, place, dst->place, s);
+  if (hipStreamSynchronize(bs.s) != hipSuccess && !rc)
+    rc = fail(e, NGPU_EHIP, "dict retire: compaction failed");
+  if (timed) {
+    float a = 0, b = 0;
+    if (!rc && hipEventElapsedTime(&a, tev[0], tev[1]) == hipSuccess &&
+        hipEventElapsedTime(&b, tev[2], tev[3]) == hipSuccess)
+      fprintf(stderr, "ngpu dict_retire m=%llu s=%llu device_us=%.1f keep_scan_us=%.1f compact_build_us=%.1f\n",
+              (unsigned long long)m, (unsigned long long)s, (a + b) * 1000.0, a * 1000.0, b * 1000.0);
+  }
+  for (hipEvent_t x : tev)
+    if (x) (void)hipEventDestroy(x);
+  (void)hipFree(scr);
+  if (rc) {
+    storage_unref(dst);
+    return rc;
+  }
+  ngpu_dict *d = new ngpu_dict();
+  d->device = base->device;
+  d->digester = base->digester;
+  d->chunk_size = base->chunk_size;
+  d->st = dst;
+  d->has_place = place && s;
+  dict_bind(d, s, nb);
+  *out = d;
+  return 0;
+}
+
+// The handle's own rows back as 80-B RAFS v6 chunk-info records: the HBM rows of
+// p (a plain dict or a replica) in pieces of 1M, the placement rows of `rows`.
+static int dict_export_records(ngpu_engine *e, const ngpu_dict *p, const DictPlace *rows,
+                               uint8_t *records) {
+  const uint64_t m = p->dev.m;
+  if (!m) return 0;
+  DeviceGuard dg(p->device);
+  BuildStream bs(p->device);
+  if (!bs.s) return fail(e, NGPU_EHIP, "chunk dict: no build stream");
+  const uint64_t batch = std::min<uint64_t>(m, 1u << 20);
+  std::vector<DictRec> h(batch);
+  for (uint64_t a = 0; a < m; a += batch) {
+    const uint64_t c = std::min(batch, m - a);
+    if (hipMemcpyAsync(h.data(), p->st->rec + a, c * sizeof(DictRec), hipMemcpyDeviceToHost, bs.s) !=
+            hipSuccess ||
+        hipStreamSynchronize(bs.s) != hipSuccess)
+      return fail(e, NGPU_EHIP, "dict export: copy of the records failed");
+    for (uint64_t i = 0; i < c; ++i) {
+      const DictRec &r = h[i];
+      RafsV6ChunkInfo x;
+      memset(&x, 0, sizeof x);
+      memcpy(x.block_id, r.digest, 32);
+      x.blob_index = r.blob;
+      x.uncompressed_size = r.usize;
+      x.uncompressed_offset = r.uoff;
+      x.index = r.index;
+      if (rows) {
+        x.compressed_offset = rows[a + i].compressed_offset;
+        x.compressed_size = rows[a + i].compressed_size;
+        x.flags = rows[a + i].flags;
+      } else {  // as ngpu_dict_load documents: stored uncompressed at offset 0
+        x.compressed_size = r.usize;
+      }
+      memcpy(records + 80 * (a + i), &x, 80);
+    }
+  }
+  return 0;
+}
+
 namespace {
 
 // RafsSuperFlags HASH_SHA256 (0x8) -> sha256, else blake3 ([nydus v2.3.0]
@@ -892,6 +1068,58 @@ int ngpu_dict_extend_bootstrap(ngpu_engine *e, ngpu_dict *base, const char *path
   });
 }
 
+int ngpu_dict_retire(ngpu_engine *e, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                     uint32_t flags, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !e || !out || (n && !blobs)) return NGPU_EINVAL;
+  return guarded([&]() -> int {
+    if (!base->parts.empty())
+      return fail(e, NGPU_EINVAL, "dict retire: a node dict is retired with ngpu_node_dict_retire");
+    if (base->device != e->device)
+      return fail(e, NGPU_EINVAL, "chunk dict lives on device %d, engine on %d", base->device,
+                  e->device);
+    if (int rc = dict_check(e, base)) return rc;
+    const DictRetirePlan plan = dict_retire_plan(base->dev.n_blobs, blobs, n);
+    if (!plan.ok)
+      return fail(e, NGPU_EINVAL, "dict retire: blob %u of a dict of %u blobs", plan.bad,
+                  base->dev.n_blobs);
+    ngpu_dict *d = nullptr;
+    if (int rc = dict_retire_records(e, base, plan.bitmap, plan.remap, plan.n_kept, base->place(),
+                                     nullptr, &d))
+      return rc;
+    d->blob_table = dict_retire_blob_table(base->blob_table, plan.remap);
+    *out = d;
+    return 0;
+  });
+}
+
+int ngpu_dict_export(ngpu_engine *e, const ngpu_dict *d, void *records, uint64_t cap,
+                     uint64_t *n_records, void *blob_table, uint32_t blob_cap, uint32_t *n_blobs) {
+  if (n_records) *n_records = d ? d->dev.m : 0;
+  if (n_blobs) *n_blobs = d ? d->dev.n_blobs : 0;
+  if (!e || !d || !n_records || !n_blobs) return NGPU_EINVAL;
+  return guarded([&]() -> int {
+    if (!d->parts.empty() && !d->replicated)
+      return fail(e, NGPU_EUNSUPP,
+                  "dict export: a partitioned node dict's rows lie on its parts (not supported yet)");
+    const ngpu_dict *p = d->parts.empty() ? d : d->parts[0];
+    const uint64_t m = d->dev.m;
+    if (!records && !cap) return 0;  // a count
+    if (cap < m || (m && !records))
+      return fail(e, NGPU_EINVAL, "dict export: room for %llu of %llu records",
+                  (unsigned long long)cap, (unsigned long long)m);
+    const bool table = blob_table && !d->blob_table.empty();
+    if (table && 256ull * blob_cap < d->blob_table.size())
+      return fail(e, NGPU_EINVAL, "dict export: room for %u of %llu blob records", blob_cap,
+                  (unsigned long long)(d->blob_table.size() / 256));
+    if (p->dev.m != m) return fail(e, NGPU_EINVAL, "dict export: replica of %llu entries, dict of %llu",
+                                   (unsigned long long)p->dev.m, (unsigned long long)m);
+    if (int rc = dict_export_records(e, p, d->place(), (uint8_t *)records)) return rc;
+    if (table) memcpy(blob_table, d->blob_table.data(), d->blob_table.size());
+    return 0;
+  });
+}
+
 int ngpu_dict_info_get(const ngpu_dict *d, ngpu_dict_info *out) {
   if (!d || !out) return NGPU_EINVAL;
   memset(out, 0, sizeof *out);
@@ -903,6 +1131,7 @@ int ngpu_dict_info_get(const ngpu_dict *d, ngpu_dict_info *out) {
     out->table_capacity = p->st->table_cap;
   }
   out->shares_base_storage = p->shares_base;
+  out->has_blob_table = !d->blob_table.empty();
   return 0;
 }
 

@@ -356,6 +356,27 @@ int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, ui
 int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
                       ngpu_dict *out);
 void storage_unref(DictStorage *st);
+// Dict retire (dict.hip): a new handle, on a storage of its own, of base's own
+// records whose blob bitmap bit is clear, blob indices through remap (both
+// tables from dict_retire_plan.hpp, of base->dev.n_blobs blobs), ids =
+// positions among the survivors; its blob count is nb, its blob table is left
+// to the caller.  place: base's placement rows, compacted into the result's
+// storage (null: it keeps none).  keep (may be null): the keep words and their
+// exclusive survivor counts, (m + 63) / 64 of each, for rows the caller
+// compacts itself with dict_retire_place.
+struct DictKeep {
+  std::vector<uint64_t> words;
+  std::vector<uint32_t> prefix;
+};
+int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector<uint32_t> &bitmap,
+                        const std::vector<uint32_t> &remap, uint32_t nb, const DictPlace *place,
+                        DictKeep *keep, ngpu_dict **out);
+// dst[0, s) = the rows of src[0, m) whose keep bit is set, on host threads.
+void dict_retire_place(const DictKeep &keep, uint64_t m, const DictPlace *src, DictPlace *dst,
+                       uint64_t s);
+// The blob table rows of the kept blobs, in order (empty table: empty).
+std::vector<uint8_t> dict_retire_blob_table(const std::vector<uint8_t> &table,
+                                            const std::vector<uint32_t> &remap);
 int read_dict_bootstrap(ngpu_engine *e, const char *path, uint64_t file_size,
                         std::vector<uint8_t> *recs_out, std::vector<uint8_t> *blobs_out,
                         uint64_t *table_at = nullptr);

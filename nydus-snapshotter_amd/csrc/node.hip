@@ -38,6 +38,7 @@
 #include <rccl/rccl.h>
 
 #include "a2a_plan.hpp"
+#include "dict_retire_plan.hpp"
 #include "engine_internal.hpp"
 
 using namespace ngpu;
@@ -378,6 +379,79 @@ int node_dict_extend(ngpu_node *node, ngpu_dict *base, const uint8_t *recs, uint
     d->blob_table = base->blob_table;
     if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
   }
+  *out = d;
+  return 0;
+}
+
+// base without the records of the listed blobs (dict.hip "dict retire"): every
+// replica retired alike, the global placement rows compacted by part 0's keep
+// words.  Partitioned dicts: a part's new global ids are ranks over all parts'
+// keep bits, which no kernel computes yet.
+int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                     ngpu_dict **out) {
+  ngpu_engine *e0 = node->eng[0];
+  const uint32_t W = (uint32_t)node->eng.size();
+  if (base->parts.empty())
+    return fail(e0, NGPU_EINVAL, "node dict retire: not a node dict (ngpu_dict_retire takes it)");
+  if (base->parts.size() != W) return fail(e0, NGPU_EINVAL, "node dict retire: dict of another node");
+  for (uint32_t o = 0; o < W; ++o)
+    if (base->parts[o]->device != node->eng[o]->device)
+      return fail(e0, NGPU_EINVAL, "node dict retire: dict of another node");
+  if (int rc = dict_check(e0, base)) return rc;
+  const DictRetirePlan plan = dict_retire_plan(base->dev.n_blobs, blobs, n);
+  if (!plan.ok)
+    return fail(e0, NGPU_EINVAL, "node dict retire: blob %u of a dict of %u blobs", plan.bad,
+                base->dev.n_blobs);
+  if (!base->replicated)
+    return fail(e0, NGPU_EUNSUPP,
+                "node dict retire: partitioned node dicts are not supported yet (replicated ones are)");
+  ngpu_dict *d = new ngpu_dict();
+  d->device = base->device;
+  d->digester = base->digester;
+  d->chunk_size = base->chunk_size;
+  d->replicated = true;
+  d->routed = base->routed;
+  DictKeep keep;
+  int rc = 0;
+  for (uint32_t o = 0; o < W && !rc; ++o) {
+    ngpu_dict *p = nullptr;
+    if ((rc = dict_retire_records(node->eng[o], base->parts[o], plan.bitmap, plan.remap, plan.n_kept,
+                                  nullptr, o == 0 ? &keep : nullptr, &p)))
+      break;
+    if (o && p->dev.m != d->parts[0]->dev.m) {
+      dict_unref(p);
+      rc = fail(e0, NGPU_EINVAL, "node dict retire: the replicas differ");
+      break;
+    }
+    d->parts.push_back(p);
+  }
+  if (!rc) {
+    const uint64_t m = base->dev.m, s = d->parts[0]->dev.m;
+    d->dev.m = s;
+    d->dev.n_blobs = plan.n_kept;
+    // the global handle: placement rows only, with a fork's room
+    DictStorage *st = new DictStorage();
+    st->device = e0->device;
+    st->rec_cap = dict_retire_rec_cap(s);
+    st->table_cap = ~0ull;
+    st->used = s;
+    d->st = st;
+    const DictPlace *rows = base->place();
+    if (rows && s) {
+      if (!(st->place = (DictPlace *)malloc(st->rec_cap * sizeof(DictPlace)))) {
+        rc = fail(e0, NGPU_ENOMEM, "chunk dict: no host memory for %llu placement rows",
+                  (unsigned long long)st->rec_cap);
+      } else {
+        dict_retire_place(keep, m, rows, st->place, s);
+        d->has_place = true;
+      }
+    }
+  }
+  if (rc) {
+    dict_unref(d);
+    return rc;
+  }
+  d->blob_table = dict_retire_blob_table(base->blob_table, plan.remap);
   *out = d;
   return 0;
 }
@@ -792,6 +866,13 @@ int ngpu_node_dict_extend(ngpu_node *node, ngpu_dict *base, const void *records,
     return node_dict_extend(node, base, (const uint8_t *)records, n, (const uint8_t *)blob_table,
                             n_blobs, out);
   });
+}
+
+int ngpu_node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                          uint32_t flags, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !node || !out || (n && !blobs)) return NGPU_EINVAL;
+  return guarded([&] { return node_dict_retire(node, base, blobs, n, out); });
 }
 
 int ngpu_node_dict_open(ngpu_node *node, const char *path, uint32_t mode, ngpu_dict **out) {

@@ -84,12 +84,15 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            "ngpu_verity_verify_tree_device", "ngpu_verity_verify_data_device", "ngpu_verity_verify_image",
            # dict extend (additive in ABI 7)
            "ngpu_dict_extend", "ngpu_dict_extend_bootstrap", "ngpu_node_dict_extend",
-           "ngpu_dict_info_get"]
+           "ngpu_dict_info_get",
+           # dict retire (additive in ABI 7)
+           "ngpu_dict_retire", "ngpu_node_dict_retire", "ngpu_dict_export"]
 
 class NgpuDictInfo(ctypes.Structure):
     _fields_ = [("entries", ctypes.c_uint64), ("blobs", ctypes.c_uint64),
                 ("record_capacity", ctypes.c_uint64), ("table_capacity", ctypes.c_uint64),
-                ("shares_base_storage", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+                ("shares_base_storage", ctypes.c_uint32), ("has_blob_table", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
 
 
 LAYER_STATS_DTYPE = np.dtype([("chunks", "<u8"), ("new_chunks", "<u8"), ("intra_chunks", "<u8"),
@@ -328,6 +331,9 @@ def lib():
     L.ngpu_dict_extend_bootstrap.argtypes = [vp, vp, ctypes.c_char_p, u32, ctypes.POINTER(vp)]
     L.ngpu_node_dict_extend.argtypes = [vp, vp, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_dict_info_get.argtypes = [vp, ctypes.POINTER(NgpuDictInfo)]
+    L.ngpu_dict_retire.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
+    L.ngpu_node_dict_retire.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
+    L.ngpu_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32)]
     L.ngpu_node_pack_open.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
     L.ngpu_node_process_device.argtypes = [vp, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp]
     L.ngpu_node_process_step.argtypes = [vp, vp, ctypes.POINTER(NgpuNodePart), u32, u32]
@@ -742,6 +748,64 @@ class ChunkDict:
         return {"entries": x.entries, "blobs": x.blobs, "record_capacity": x.record_capacity,
                 "table_capacity": x.table_capacity,
                 "shares_base_storage": bool(x.shares_base_storage)}
+
+    def _has_blob_table(self) -> bool:
+        x = NgpuDictInfo()
+        rc = lib().ngpu_dict_info_get(self._h, ctypes.byref(x))
+        if rc:
+            raise NgpuError(rc, "dict_info")
+        return bool(x.has_blob_table)
+
+    def export(self, engine=None):
+        """ngpu_dict_export: (records as rafs.CHUNK_INFO_DTYPE in table order,
+        the 256-B blob records as bytes or None when the dict has only a blob
+        count); dict_create over them answers as this dict.  engine: the Engine
+        to report through (default: the one that made the dict; a node dict
+        takes one of its node's, see Node.dict_export)."""
+        from . import rafs
+        e = engine if engine is not None else self._engine()
+        L = lib()
+        m, nb = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        e._check(L.ngpu_dict_export(e._h, self._h, None, 0, ctypes.byref(m), None, 0, ctypes.byref(nb)),
+                 "dict_export")
+        recs = np.zeros(m.value, rafs.CHUNK_INFO_DTYPE)
+        table = np.zeros(256 * nb.value, np.uint8) if nb.value and self._has_blob_table() else None
+        room = recs if m.value else np.zeros(1, rafs.CHUNK_INFO_DTYPE)  # (not the counting call)
+        e._check(L.ngpu_dict_export(e._h, self._h, _ptr(room.view(np.uint8).reshape(-1)), len(room),
+                                    ctypes.byref(m), _ptr(table), nb.value if table is not None else 0,
+                                    ctypes.byref(nb)), "dict_export")
+        return recs, (None if table is None else table.tobytes())
+
+    def _blob_indices(self, blobs, engine=None):
+        """ints as they are; 64-hex blob ids through the exported blob table."""
+        want = list(blobs)
+        if not any(isinstance(b, (str, bytes)) for b in want):
+            return [int(b) for b in want]
+        from . import rafs
+        _, table = self.export(engine)
+        ids = [] if table is None else [x.decode() for x in np.frombuffer(table, rafs.BLOB_DTYPE)["blob_id"]]
+        out = []
+        for b in want:
+            if isinstance(b, (str, bytes)):
+                s = b.decode() if isinstance(b, bytes) else b
+                if s not in ids:
+                    raise ValueError(f"blob {s} is not in the dict's blob table")
+                out.append(ids.index(s))
+            else:
+                out.append(int(b))
+        return out
+
+    def retire(self, blobs) -> "ChunkDict":
+        """ngpu_dict_retire: a new dict of this one's entries without those of
+        the listed blobs (inner blob indices, or 64-hex blob ids looked up in
+        the blob table; an id that is not there raises ValueError).  This handle
+        stays as it is."""
+        e = self._engine()
+        idx = np.asarray(self._blob_indices(blobs), np.uint32)
+        h = ctypes.c_void_p()
+        e._check(lib().ngpu_dict_retire(e._h, self._h, _ptr(idx) if len(idx) else None, len(idx), 0,
+                                        ctypes.byref(h)), "dict_retire")
+        return ChunkDict(h, e)
 
     def _engine(self):
         if self._eng is None or not self._eng._h:
@@ -1419,6 +1483,20 @@ class Node:
         self._err(lib().ngpu_node_dict_extend(self._h, base._h, _ptr(r), r.size // 80, _ptr(b),
                                               0 if b is None else b.size // 256, 0, ctypes.byref(h)),
                   "node_dict_extend")
+        return ChunkDict(h)
+
+    def dict_export(self, d: ChunkDict):
+        """ChunkDict.export of a (replicated) node dict."""
+        return d.export(self.engines[0])
+
+    def dict_retire(self, base: ChunkDict, blobs) -> ChunkDict:
+        """ngpu_node_dict_retire: a new node dict of base's entries without those
+        of the listed blobs (indices or 64-hex blob ids, as ChunkDict.retire).
+        Replicated node dicts; a partitioned one raises NgpuError (EUNSUPP)."""
+        idx = np.asarray(base._blob_indices(blobs, self.engines[0]), np.uint32)
+        h = ctypes.c_void_p()
+        self._err(lib().ngpu_node_dict_retire(self._h, base._h, _ptr(idx), len(idx), 0,
+                                              ctypes.byref(h)), "node_dict_retire")
         return ChunkDict(h)
 
     def pack(self, dict=None, retain: bool = False) -> "PackWriter":

@@ -18,7 +18,7 @@ usage:
   python -m nydus_gpu.inspect --tree FILE     # JSON dump of the inode tree
   python -m nydus_gpu.inspect --diff A B      # exit 0 iff the chunk sets match
   python -m nydus_gpu.inspect --diff --tree A B  # exit 0 iff the trees match
-  python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP]... [--chunk-size N] [--digester D]
+  python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP]... [--retire BLOBID]... [--chunk-size N] [--digester D]
                                               # re-digest STREAM's chunks on the GPU; exit 1 if any is bad
   python -m nydus_gpu.inspect --verity IMAGE [--append]
                                               # the dm-verity tree of a block image; prints its options line
@@ -35,6 +35,9 @@ the `--dict` chunk-dict bootstrap (without one they are counted as skipped).
 Several `--dict` are folded into one dict in the order given (the first is
 opened, each further one appended with ChunkDict.extend_bootstrap), as a
 conversion run folds each converted image into its chunk dict.
+Every `--retire BLOBID` (64 hex characters, or an inner blob index) then drops
+that blob's records from the folded dict (ChunkDict.retire), as a registry's
+garbage collection does: DICT records of a retired blob no longer resolve.
 The digester, chunk size and RAFS version default to the stream's own; the
 report is printed as JSON.
 
@@ -148,9 +151,10 @@ def diff(a: dict, b: dict, fields=("digest", "blob_id", "uncompressed_size")) ->
 
 
 def check(path: str, dict_path=None, chunk_size: int = 0, digester: str = None,
-          max_bad: int = 64) -> dict:
+          max_bad: int = 64, retire=None) -> dict:
     """Engine.check of the stream in `path` on GPU 0 (the report dict).
-    dict_path: a chunk-dict bootstrap, or a list of them folded into one dict."""
+    dict_path: a chunk-dict bootstrap, or a list of them folded into one dict;
+    retire: blob ids (or inner indices) whose records leave the folded dict first."""
     from ._lib import Engine
     data = np.fromfile(path, np.uint8)
     boot = bootstrap_bytes(data)
@@ -170,6 +174,12 @@ def check(path: str, dict_path=None, chunk_size: int = 0, digester: str = None,
                 grown = dct.extend_bootstrap(p)
                 dct.release()
                 dct = grown
+            if retire:
+                if dct is None:
+                    raise ValueError("--retire needs a --dict")
+                kept = dct.retire([int(b) if str(b).isdigit() and len(str(b)) < 64 else b for b in retire])
+                dct.release()
+                dct = kept
             return eng.check(data, dict=dct, max_bad=max_bad)
         finally:
             if dct is not None:
@@ -240,6 +250,8 @@ def main(argv=None) -> int:
     ap.add_argument("--check", metavar="STREAM", help="re-digest a Pack output stream's chunks on the GPU")
     ap.add_argument("--dict", metavar="BOOTSTRAP", action="append",
                     help="--check: chunk-dict bootstrap for DICT records (repeat to fold several into one dict)")
+    ap.add_argument("--retire", metavar="BLOBID", action="append",
+                    help="--check: drop this blob's records from the folded dict first (repeatable)")
     ap.add_argument("--chunk-size", type=lambda x: int(x, 0), default=0, help="--check: engine chunk size")
     ap.add_argument("--digester", choices=("blake3", "sha256"), help="--check: engine digester")
     ap.add_argument("--verity", metavar="IMAGE", help="dm-verity tree of a block image on the GPU")
@@ -260,7 +272,7 @@ def main(argv=None) -> int:
         except ImportError:
             pass
         try:
-            rep = check(args.check, args.dict, args.chunk_size, args.digester)
+            rep = check(args.check, args.dict, args.chunk_size, args.digester, retire=args.retire)
         except (NgpuError, ValueError) as e:
             print(f"check: {e}", file=sys.stderr)
             return 2
