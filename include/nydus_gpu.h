@@ -296,6 +296,84 @@ int ngpu_dict_extend(ngpu_engine *eng, ngpu_dict *base, const void *records, uin
  * ngpu_dict_open's compatibility checks (digester flag, chunk size, FsVersion 6). */
 int ngpu_dict_extend_bootstrap(ngpu_engine *eng, ngpu_dict *base, const char *path,
                                uint32_t flags, ngpu_dict **out);
+/* ---- dict extend from device arrays (additive in ABI 7) ----
+ * ngpu_dict_extend for rows that lie in HBM as ngpu_dict_create_device's arrays
+ * (d_uoff and d_chunk_index may be NULL; the arrays must be complete when the
+ * call is made).  out answers every probe, Pack, Check, stats field and export as
+ * ngpu_dict_extend over the same rows given as 80-B records without a blob table:
+ * blob_index += blobs(base), entry ids entries(base) + position, in place or on a
+ * larger storage exactly as ngpu_dict_extend decides.  Nothing is staged: one
+ * kernel writes the records behind base's, the table insert (or build) follows.
+ * n_blobs is the caller's word for the new rows' blob count, as in
+ * ngpu_dict_create_device; blobs(out) = blobs(base) + n_blobs, at most 2^20.
+ * The call carries no blob table and no compressed placements, so a base that
+ * holds a blob table is NGPU_EINVAL (ngpu_dict_extend's rule: exactly one side
+ * with a table; a base of 0 blobs is fine), and so is a base that keeps
+ * placements when n > 0: nothing is dropped silently.  n == 0 returns a handle
+ * equal to base.  Also NGPU_EINVAL, all with *out = NULL: base == NULL,
+ * flags != 0, n without d_digests / d_usize / d_blob_index, d_digests not
+ * 16-byte aligned, a node dict.  The device work runs on a stream of the
+ * library's own, outside the engine lock, and is complete on return; one fold
+ * or extend_device runs at a time per engine. */
+int ngpu_dict_extend_device(ngpu_engine *eng, ngpu_dict *base, const uint8_t *d_digests,
+                            const uint32_t *d_usize, const uint32_t *d_blob_index,
+                            const uint32_t *d_chunk_index, const uint64_t *d_uoff, uint64_t n,
+                            uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
+/* ---- dict fold: grow a dict from a dedup call's results (additive in ABI 7) ----
+ * out = base followed by one record per chunk of d_results[0, n) whose kind ==
+ * NGPU_NEW, in chunk order (layers are contiguous in chunk order: layer order,
+ * then stream order inside a layer).  d_results / d_chunks are the device tables
+ * of an ngpu_process*_device / ngpu_dedup*_device call, d_layer_first its
+ * n_layers + 1 device u64 layer cuts (NULL or n_layers <= 1: one layer of n
+ * chunks).  Equal, for every probe, Pack, Check, stats field and export, to
+ * ngpu_dict_extend over the host rows built from each NEW chunk c:
+ *   block_id            = d_results[c].digest
+ *   uncompressed_size   = d_chunks[c].length
+ *   blob_index          = r(l): the number of layers before c's layer l that hold
+ *                         at least one NEW chunk (every such layer is one new
+ *                         blob; after the shift the record's blob is
+ *                         blobs(base) + r(l))
+ *   index               = d_results[c].index
+ *   uncompressed_offset = d_results[c].uncompressed_offset
+ *   compressed_offset / compressed_size / flags = placements[position among the
+ *                         new records] (host rows), or csize = usize, offset 0,
+ *                         flags 0 when the dict keeps none
+ * INTRA and DICT chunks add nothing.  First entry still wins; base is untouched
+ * and not released; handles older than out stay blind to an in-place append;
+ * share or fork as ngpu_dict_extend decides.  flags must be 0.
+ *
+ * The NEW chunks k and the layers with one, b, are counted on the device (one
+ * keep bit per chunk, a scan, a pass over the layers) and come back in one small
+ * copy, the call's only mid-way wait; everything below is then checked before a
+ * byte of any storage is written and before a record slot is reserved, so a
+ * refused call leaves base and its storage as they were.  Refused with
+ * NGPU_EINVAL and *out = NULL:
+ *   a kind other than NEW / INTRA / DICT anywhere in [0, n) (DIGESTED, UNHASHED,
+ *   garbage): the message names the first such chunk;
+ *   a NEW chunk with length 0 or > chunk_size;
+ *   layer cuts with first[0] != 0, first[n_layers] != n or a decreasing entry;
+ *   d_results not 16-byte aligned, d_chunks / d_layer_first not 8-byte aligned,
+ *   n without d_results / d_chunks;
+ *   placements with n_placements != k; k > 0 and base keeps placements but none
+ *   are given; base has records and keeps none but some are given (an empty
+ *   base goes with either);
+ *   the blob table: ngpu_dict_extend's rule, and n_blobs == b when one is
+ *   passed (n_blobs without blob_table is refused);
+ *   ngpu_dict_extend's size limits; a node dict; flags != 0.
+ * k == 0 returns a handle equal to base.  The device work runs on a stream of the
+ * library's own, outside the engine lock, and is complete on return; it does not
+ * wait for the caller's streams, so the stream that wrote the results must have
+ * been synchronised (as for ngpu_dict_create_device).  An in-place fold
+ * allocates and frees no device memory. */
+typedef struct {
+  uint64_t compressed_offset;
+  uint32_t compressed_size;
+  uint32_t flags; /* RAFS v6 chunk flags (bit 0: compressed) */
+} ngpu_dict_place;
+int ngpu_dict_fold(ngpu_engine *eng, ngpu_dict *base, const ngpu_result *d_results,
+                   const ngpu_chunk *d_chunks, uint64_t n, const uint64_t *d_layer_first,
+                   uint64_t n_layers, const ngpu_dict_place *placements, uint64_t n_placements,
+                   const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
 /* ---- dict retire: drop the records of deleted blobs from a dict ----
  * out = base without the records of the listed inner blobs (blobs[0, n), any
  * order, duplicates allowed).  Equal, for every probe, Pack, Check, stats field

@@ -307,6 +307,42 @@ void launch_dict_keep_scan(const DictRec *rec, uint64_t m, const uint32_t *bitma
 void launch_dict_compact(const DictRec *rec, uint64_t m, const uint64_t *words,
                          const uint32_t *prefix, const uint32_t *remap, uint32_t n_blobs,
                          DictRec *out, uint64_t n_out, hipStream_t s);
+// Launch 2 alone (dict fold runs it over its own keep words): cnt[0, nw) ->
+// exclusive prefixes in place, the total to sums[nt], nt = ceil(nw /
+// kRetireScanTile); sums: nt + 1 words.
+void launch_retire_scan(uint32_t *cnt, uint64_t nw, uint64_t *sums, hipStream_t s);
+
+// dict_fold.hip (dict fold, dict.hip).  ctr: kFoldCtrWords u64, zeroed on s by
+// the caller before launch_fold_keep_scan.
+constexpr int kFoldK = 0;         // NEW chunks of the call
+constexpr int kFoldBlobs = 1;     // layers with a NEW chunk
+constexpr int kFoldBadKind = 2;   // chunks whose kind is none of NEW / INTRA / DICT
+constexpr int kFoldBadKind1 = 3;  // ~(the smallest such chunk id) (atomic max), 0 = none
+constexpr int kFoldBadLen = 4;    // NEW chunks of length 0 or > chunk_size
+constexpr int kFoldBadLen1 = 5;   // ~(the smallest such chunk id), 0 = none
+constexpr int kFoldBadLayer1 = 6; // ~(the smallest layer whose bounds are out of order), 0 = none
+constexpr int kFoldCtrWords = 8;
+// Launches 1-3: keep word + NEW count per 64 chunks of res[0, n) (a lane per
+// chunk; kinds and the NEW chunks' lengths are checked in the same pass), the
+// scan of the counts, then each layer's blob rank (the number of earlier layers
+// with a NEW chunk) into lrank[0, L) and the totals into ctr.  lfirst: device
+// u64[L + 1], checked here (null: one layer of n chunks, L = 1).  words / cnt:
+// (n + 63) / 64 entries; sums: dict_retire_scan_tiles(n) + 1 words.
+void launch_fold_keep_scan(const ngpu_result *res, const ngpu_chunk *chunks, uint64_t n,
+                           uint32_t chunk_size, const uint64_t *lfirst, uint64_t L, uint64_t *words,
+                           uint32_t *cnt, uint64_t *sums, uint32_t *lrank, uint64_t *ctr,
+                           hipStream_t s);
+// Launch 4: NEW chunk c -> out[prefix[c / 64] + popc(word below c)], out = rec + m:
+// digest, index and uoff from its result, usize from its descriptor, blob =
+// blob0 + lrank[its layer], gid = gid0 + position.  k bounds the writes.
+void launch_fold_scatter(const ngpu_result *res, const ngpu_chunk *chunks, uint64_t n,
+                         const uint64_t *words, const uint32_t *prefix, const uint64_t *lfirst,
+                         uint64_t L, const uint32_t *lrank, uint32_t blob0, uint32_t gid0,
+                         DictRec *out, uint64_t k, hipStream_t s);
+// launch_dict_pack at an offset: blob0 added to every blob index, gid = gid0 + i.
+void launch_dict_pack_at(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,
+                         const uint32_t *index, const uint64_t *uoff, uint64_t n, uint32_t blob0,
+                         uint32_t gid0, DictRec *out, hipStream_t s);
 
 // Device workspace, grown on demand and owned by the engine.
 struct Workspace {

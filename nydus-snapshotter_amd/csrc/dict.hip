@@ -14,7 +14,9 @@
 // (offset, size, flags) stays on the host: only the blob writer reads it.
 // Records, table and placement rows belong to a reference-counted DictStorage;
 // a handle is immutable, and ngpu_dict_extend ("dict extend" below) puts a new
-// handle on the same storage when there is room, else on a larger one.
+// handle on the same storage when there is room, else on a larger one; so do
+// ngpu_dict_fold and ngpu_dict_extend_device ("dict fold"), whose new records
+// are written by a kernel from tables that already lie in HBM.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
@@ -29,6 +31,7 @@
 #include <thread>
 
 #include "blob.hpp"
+#include "dict_fold_plan.hpp"
 #include "dict_grow_plan.hpp"
 #include "dict_retire_plan.hpp"
 #include "engine_internal.hpp"
@@ -317,22 +320,28 @@ int dict_extend_check(ngpu_engine *e, const ngpu_dict *base, const uint8_t *recs
     nb = std::max(nb, r->blob_index + 1);
   }
   if (n_blobs) nb = n_blobs;
+  return dict_extend_check_blobs(e, base, k, nb, blobs && n_blobs, n_blobs, nb_out, with_table);
+}
+
+// The half of dict_extend_check that needs no records (a fold counts its blobs
+// on the device): nb more blobs against the 2^20 limit, and the blob table rule
+// (dict_fold_plan.hpp): kept only when both sides have one; a base of 0 blobs
+// goes with either, and so does a call that adds nothing.
+int dict_extend_check_blobs(ngpu_engine *e, const ngpu_dict *base, uint64_t k, uint32_t nb,
+                            bool call_has, uint32_t n_blobs, uint32_t *nb_out, bool *with_table) {
+  const uint64_t m = base->dev.m;
+  if (m >= kDictMaxEntries || k >= kDictMaxEntries - m)
+    return fail(e, NGPU_EINVAL, "chunk dict too large (%llu entries)", (unsigned long long)(m + k));
   if (nb > (1u << 20) || base->dev.n_blobs + nb > (1u << 20))
     return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", base->dev.n_blobs + nb - 1);
-  // the blob table: kept only when both sides have one; a base of 0 blobs goes
-  // with either, and so does a call that adds nothing
-  const bool base_has = !base->blob_table.empty(), call_has = blobs && n_blobs;
-  if (base->dev.n_blobs == 0 && !base_has) {
-    *with_table = call_has;
-  } else if (k == 0 && n_blobs == 0) {
-    *with_table = base_has;
-  } else if (base_has != call_has) {
+  const DictTableRule r =
+      dict_table_rule(base->dev.n_blobs, !base->blob_table.empty(), call_has, k, n_blobs);
+  if (r < 0)
     return fail(e, NGPU_EINVAL,
-                base_has ? "dict extend: the base has a blob table, the new records come without one"
-                         : "dict extend: the base has no blob table, the new records come with one");
-  } else {
-    *with_table = base_has;
-  }
+                r == kTableBaseOnly
+                    ? "dict extend: the base has a blob table, the new records come without one"
+                    : "dict extend: the base has no blob table, the new records come with one");
+  *with_table = r == kTableKept;
   *nb_out = base->dev.n_blobs + nb;
   return 0;
 }
@@ -340,9 +349,21 @@ int dict_extend_check(ngpu_engine *e, const ngpu_dict *base, const uint8_t *recs
 int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
                         uint32_t blob0, uint32_t nb, const uint32_t *gids, bool place,
                         ngpu_dict **out) {
+  DictRowSource src;
+  src.recs = recs;
+  src.gids = gids;
+  src.blob0 = blob0;
+  return dict_extend_rows(e, base, src, k, nb, place, out);
+}
+
+int dict_extend_rows(ngpu_engine *e, ngpu_dict *base, const DictRowSource &src, uint64_t k,
+                     uint32_t nb, bool place, ngpu_dict **out) {
   DeviceGuard dg(e->device);
   DictStorage *st = base->st;
   const uint64_t m = base->dev.m;
+  const uint8_t *recs = src.recs;
+  const uint32_t *gids = src.gids;
+  const bool staged = !src.write;  // host records: upload + unpack
   const bool want_place = place && (base->has_place || m == 0);
   DictGrowPlan plan;
   bool share = k == 0;  // nothing to write: another handle on the same entries
@@ -367,14 +388,16 @@ int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, ui
   }
   int rc = 0;
   if (k) {
-    BuildStream bs(e->device);
+    // a device source brings the stream its inputs are ordered on
+    std::unique_ptr<BuildStream> own(src.stream ? nullptr : new BuildStream(e->device));
+    const hipStream_t bs = src.stream ? src.stream : own->s;
     const uint64_t batch = std::min<uint64_t>(k, 1u << 20);
     uint8_t *tmp = nullptr;
     uint32_t *tmp_gid = nullptr;
-    if (!bs.s) {
+    if (!bs) {
       rc = fail(e, NGPU_EHIP, "chunk dict: no build stream");
-    } else if (hipMalloc((void **)&tmp, batch * 80) != hipSuccess ||
-               (gids && hipMalloc((void **)&tmp_gid, batch * 4) != hipSuccess)) {
+    } else if (staged && (hipMalloc((void **)&tmp, batch * 80) != hipSuccess ||
+                          (gids && hipMalloc((void **)&tmp_gid, batch * 4) != hipSuccess))) {
       (void)hipGetLastError();
       rc = fail(e, NGPU_ENOMEM, "chunk dict: staging allocation failed");
     }
@@ -391,51 +414,67 @@ int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, ui
     if (!rc && trace)
       for (hipEvent_t &x : tev)
         if (hipEventCreate(&x) != hipSuccess) x = nullptr;
-    if (!share && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs.s);
+    if (!share && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs);
     if (!rc && !share && m &&
-        hipMemcpyAsync(dst->rec, st->rec, m * sizeof(DictRec), hipMemcpyDeviceToDevice, bs.s) !=
+        hipMemcpyAsync(dst->rec, st->rec, m * sizeof(DictRec), hipMemcpyDeviceToDevice, bs) !=
             hipSuccess)
       rc = fail(e, NGPU_EHIP, "chunk dict: copy of the base's records failed");
     if (!rc && want_place) {
       if (!share && base->has_place) memcpy(dst->place, st->place, m * sizeof(DictPlace));
-      for (uint64_t i = 0; i < k; ++i) {
-        const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-        dst->place[m + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+      if (!staged) {
+        if (src.rows) memcpy(dst->place + m, src.rows, k * sizeof(DictPlace));
+      } else {
+        for (uint64_t i = 0; i < k; ++i) {
+          const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
+          dst->place[m + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+        }
       }
     }
     // launch 1 (per batch of <= 1M records): rec[m + a ..) from the 80-B records
-    for (uint64_t a = 0; a < k && !rc; a += batch) {
+    for (uint64_t a = 0; staged && a < k && !rc; a += batch) {
       const uint64_t c = std::min(batch, k - a);
-      if (hipMemcpyAsync(tmp, recs + 80 * a, c * 80, hipMemcpyHostToDevice, bs.s) != hipSuccess ||
-          (gids && hipMemcpyAsync(tmp_gid, gids + a, c * 4, hipMemcpyHostToDevice, bs.s) !=
+      if (hipMemcpyAsync(tmp, recs + 80 * a, c * 80, hipMemcpyHostToDevice, bs) != hipSuccess ||
+          (gids && hipMemcpyAsync(tmp_gid, gids + a, c * 4, hipMemcpyHostToDevice, bs) !=
                        hipSuccess)) {
         rc = fail(e, NGPU_EHIP, "chunk dict: upload failed");
         break;
       }
-      if (share && a == 0 && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs.s);
-      launch_dict_unpack(tmp, c, gids ? tmp_gid : nullptr, (uint32_t)(m + a), dst->rec + m + a, bs.s,
-                         blob0);
+      if (share && a == 0 && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs);
+      launch_dict_unpack(tmp, c, gids ? tmp_gid : nullptr, (uint32_t)(m + a), dst->rec + m + a, bs,
+                         src.blob0);
       // the next batch overwrites tmp (one batch: the sync after the inserts serves)
-      if (a + c < k && hipStreamSynchronize(bs.s) != hipSuccess)
+      if (a + c < k && hipStreamSynchronize(bs) != hipSuccess)
         rc = fail(e, NGPU_EHIP, "chunk dict: unpack failed");
+    }
+    // (device source) launch 1: its own kernel writes rec[m, m + k)
+    if (!staged && !rc) {
+      if (share && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs);
+      src.write(src, dst->rec + m, m, bs);
+      if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: record write failed");
     }
     // launch 2, after every record is written: the new ids into the live table
     // (share), or the whole table of the new storage (fork)
     if (!rc) {
       if (share)
-        launch_dict_insert_range(dst->rec, m, m + k, dst->table, dst->table_cap, bs.s);
+        launch_dict_insert_range(dst->rec, m, m + k, dst->table, dst->table_cap, bs);
       else
-        launch_dict_build(dst->rec, m + k, dst->table, dst->table_cap, bs.s);
+        launch_dict_build(dst->rec, m + k, dst->table, dst->table_cap, bs);
       if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: table insert failed");
     }
-    if (tev[0] && tev[1]) (void)hipEventRecord(tev[1], bs.s);
-    if (bs.s && hipStreamSynchronize(bs.s) != hipSuccess && !rc)
+    if (tev[0] && tev[1]) (void)hipEventRecord(tev[1], bs);
+    if (bs && hipStreamSynchronize(bs) != hipSuccess && !rc)
       rc = fail(e, NGPU_EHIP, "chunk dict: extend failed");
     if (tev[0] && tev[1]) {
       float ms = 0;
-      if (!rc && hipEventElapsedTime(&ms, tev[0], tev[1]) == hipSuccess)
-        fprintf(stderr, "ngpu dict_extend %s m=%llu k=%llu device_us=%.1f\n", share ? "share" : "fork",
-                (unsigned long long)m, (unsigned long long)k, ms * 1000.0);
+      if (!rc && hipEventElapsedTime(&ms, tev[0], tev[1]) == hipSuccess) {
+        if (staged)
+          fprintf(stderr, "ngpu dict_extend %s m=%llu k=%llu device_us=%.1f\n", share ? "share" : "fork",
+                  (unsigned long long)m, (unsigned long long)k, ms * 1000.0);
+        else  // the fold's keep + scan ran before the counts came back
+          fprintf(stderr, "ngpu %s %s m=%llu k=%llu n=%llu device_us=%.1f keep_scan_us=%.1f\n", src.name,
+                  share ? "share" : "fork", (unsigned long long)m, (unsigned long long)k,
+                  (unsigned long long)src.n, ms * 1000.0 + src.pre_us, src.pre_us);
+      }
     }
     for (hipEvent_t x : tev)
       if (x) (void)hipEventDestroy(x);
@@ -1065,6 +1104,259 @@ int ngpu_dict_extend_bootstrap(ngpu_engine *e, ngpu_dict *base, const char *path
     if (int rc = read_dict_bootstrap(e, path, (uint64_t)st.st_size, &recs, &blobs)) return rc;
     return dict_extend(e, base, recs.data(), recs.size() / 80, blobs.data(),
                        (uint32_t)(blobs.size() / 256), out);
+  });
+}
+
+// ---- dict fold -----------------------------------------------------------------
+// An extend whose records never leave HBM (dict_fold.hip): the source of
+// dict_extend_rows is a kernel that writes rec[m, m + k) from the call's result
+// table (ngpu_dict_fold) or from SoA arrays (ngpu_dict_extend_device), so the
+// share / fork decision, the storage and the handle are extend's own.  A fold
+// learns k and its blob count from the device: launches 1-3 run first, one 64-B
+// copy brings the counters back (the call's only mid-way sync), everything is
+// checked on the host, and only then is `used` reserved and a storage written.
+// Both calls run on the engine's fold stream with its kept scratch (fold_mu):
+// no device allocation or free on the in-place path.
+
+static_assert(sizeof(ngpu_dict_place) == sizeof(DictPlace) &&
+                  offsetof(ngpu_dict_place, compressed_size) == offsetof(DictPlace, compressed_size) &&
+                  offsetof(ngpu_dict_place, flags) == offsetof(DictPlace, flags),
+              "ngpu_dict_place is a DictPlace");
+
+// e->fold_mu held: the fold stream, and at least `bytes` of scratch.
+static int fold_lane(ngpu_engine *e, uint64_t bytes) {
+  if (!e->fold_stream &&
+      hipStreamCreateWithFlags(&e->fold_stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    e->fold_stream = nullptr;
+    return fail(e, NGPU_EHIP, "chunk dict: no build stream");
+  }
+  if (bytes > e->fold_scr_cap) {
+    // (nothing of an earlier fold still runs: each is complete when it returns)
+    if (e->fold_scr) (void)hipFree(e->fold_scr);
+    e->fold_scr = nullptr;
+    e->fold_scr_cap = 0;
+    const uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 1u << 16);
+    if (hipMalloc((void **)&e->fold_scr, want) != hipSuccess) {
+      (void)hipGetLastError();
+      e->fold_scr = nullptr;
+      return fail(e, NGPU_ENOMEM, "dict fold: scratch allocation failed");
+    }
+    e->fold_scr_cap = want;
+  }
+  return 0;
+}
+
+namespace {
+struct FoldArgs {
+  const ngpu_result *res;
+  const ngpu_chunk *chunks;
+  uint64_t n;
+  const uint64_t *words;
+  const uint32_t *prefix;
+  const uint64_t *lfirst;
+  uint64_t L;
+  const uint32_t *lrank;
+  uint32_t blob0;
+  uint64_t k;
+};
+void fold_write(const DictRowSource &src, DictRec *dst, uint64_t m, hipStream_t s) {
+  const FoldArgs &a = *static_cast<const FoldArgs *>(src.arg);
+  launch_fold_scatter(a.res, a.chunks, a.n, a.words, a.prefix, a.lfirst, a.L, a.lrank, a.blob0,
+                      (uint32_t)m, dst, a.k, s);
+}
+struct PackArgs {
+  const uint8_t *dg;
+  const uint32_t *us, *bl, *ix;
+  const uint64_t *uo;
+  uint64_t n;
+  uint32_t blob0;
+};
+void pack_write(const DictRowSource &src, DictRec *dst, uint64_t m, hipStream_t s) {
+  const PackArgs &a = *static_cast<const PackArgs *>(src.arg);
+  launch_dict_pack_at(a.dg, a.us, a.bl, a.ix, a.uo, a.n, a.blob0, (uint32_t)m, dst, s);
+}
+}  // namespace
+
+static int dict_fold_base_check(ngpu_engine *e, const ngpu_dict *base, const char *what) {
+  if (!base->parts.empty()) return fail(e, NGPU_EINVAL, "%s: node dicts are not supported", what);
+  if (base->device != e->device)
+    return fail(e, NGPU_EINVAL, "chunk dict lives on device %d, engine on %d", base->device,
+                e->device);
+  return dict_check(e, base);
+}
+
+static int dict_extend_device(ngpu_engine *e, ngpu_dict *base, const PackArgs &a, uint32_t n_blobs,
+                              ngpu_dict **out) {
+  if (int rc = dict_fold_base_check(e, base, "dict extend_device")) return rc;
+  ngpu_dict *d = nullptr;
+  if (a.n == 0) {  // a handle equal to base
+    if (int rc = dict_extend_rows(e, base, DictRowSource{}, 0, base->dev.n_blobs, base->has_place, &d))
+      return rc;
+    d->blob_table = base->blob_table;
+    *out = d;
+    return 0;
+  }
+  uint32_t nb = 0;
+  bool with_table = false;
+  if (int rc = dict_extend_check_blobs(e, base, a.n, n_blobs, false, n_blobs, &nb, &with_table))
+    return rc;
+  if (base->has_place)
+    return fail(e, NGPU_EINVAL,
+                "dict extend_device: the base keeps compressed placements, device arrays carry none");
+  std::lock_guard<std::mutex> lane(e->fold_mu);
+  DeviceGuard dg(e->device);
+  if (int rc = fold_lane(e, 0)) return rc;
+  PackArgs args = a;
+  args.blob0 = base->dev.n_blobs;
+  DictRowSource src;
+  src.write = pack_write;
+  src.arg = &args;
+  src.stream = e->fold_stream;
+  src.name = "dict_extend_device";
+  src.n = a.n;
+  if (int rc = dict_extend_rows(e, base, src, a.n, nb, false, &d)) return rc;
+  *out = d;
+  return 0;
+}
+
+int ngpu_dict_extend_device(ngpu_engine *e, ngpu_dict *base, const uint8_t *d_digests,
+                            const uint32_t *d_usize, const uint32_t *d_blob_index,
+                            const uint32_t *d_chunk_index, const uint64_t *d_uoff, uint64_t n,
+                            uint32_t n_blobs, uint32_t flags, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !e || !out || (n && (!d_digests || !d_usize || !d_blob_index)) ||
+      ((uintptr_t)d_digests & 15))
+    return NGPU_EINVAL;
+  return guarded([&] {
+    return dict_extend_device(e, base, PackArgs{d_digests, d_usize, d_blob_index, d_chunk_index, d_uoff, n, 0},
+                              n_blobs, out);
+  });
+}
+
+static int dict_fold(ngpu_engine *e, ngpu_dict *base, const ngpu_result *d_res,
+                     const ngpu_chunk *d_chunks, uint64_t n, const uint64_t *d_lfirst, uint64_t L,
+                     const ngpu_dict_place *placements, uint64_t n_placements, const uint8_t *blobs,
+                     uint32_t n_blobs, ngpu_dict **out) {
+  if (int rc = dict_fold_base_check(e, base, "dict fold")) return rc;
+  if (n >= kDictMaxEntries || L >= kDictMaxEntries)
+    return fail(e, NGPU_EINVAL, "dict fold: %llu chunks in %llu layers in one call",
+                (unsigned long long)n, (unsigned long long)L);
+  if (L <= 1) d_lfirst = nullptr, L = 1;  // one layer of n chunks
+  std::lock_guard<std::mutex> lane(e->fold_mu);
+  DeviceGuard dg(e->device);
+  // scratch: keep words, tile sums (+ the total), counters, word counts /
+  // prefixes, layer ranks
+  const uint64_t nw = (n + 63) / 64, nt = dict_retire_scan_tiles(n);
+  const uint64_t o_sums = 8 * nw, o_ctr = o_sums + 8 * (nt + 1), o_cnt = o_ctr + 8 * kFoldCtrWords,
+                 o_rank = o_cnt + 4 * nw, bytes = o_rank + 4 * L;
+  if (int rc = fold_lane(e, bytes)) return rc;
+  const hipStream_t s = e->fold_stream;
+  uint8_t *scr = e->fold_scr;
+  uint64_t *d_words = (uint64_t *)scr, *d_sums = (uint64_t *)(scr + o_sums),
+           *d_ctr = (uint64_t *)(scr + o_ctr);
+  uint32_t *d_cnt = (uint32_t *)(scr + o_cnt), *d_rank = (uint32_t *)(scr + o_rank);
+  static const bool trace = [] {
+    const char *v = getenv("NGPU_DICT_TRACE");
+    return v && v[0] == '1';
+  }();
+  hipEvent_t tev[2] = {};
+  if (trace)
+    for (hipEvent_t &x : tev)
+      if (hipEventCreate(&x) != hipSuccess) x = nullptr;
+  const bool timed = tev[0] && tev[1];
+  uint64_t ctr[kFoldCtrWords] = {};
+  int rc = 0;
+  if (hipMemsetAsync(d_ctr, 0, 8 * kFoldCtrWords, s) != hipSuccess)
+    rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
+  if (!rc) {
+    if (timed) (void)hipEventRecord(tev[0], s);
+    launch_fold_keep_scan(d_res, d_chunks, n, e->cfg.chunk_size, d_lfirst, L, d_words, d_cnt, d_sums,
+                          d_rank, d_ctr, s);
+    if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
+    if (timed) (void)hipEventRecord(tev[1], s);
+  }
+  // k, b and the refusals in one small copy: the call's only mid-way sync
+  if (!rc && (hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, s) != hipSuccess ||
+              hipStreamSynchronize(s) != hipSuccess))
+    rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
+  float pre_ms = 0;
+  if (!rc && timed && hipEventElapsedTime(&pre_ms, tev[0], tev[1]) != hipSuccess) pre_ms = 0;
+  for (hipEvent_t x : tev)
+    if (x) (void)hipEventDestroy(x);
+  if (rc) return rc;
+  const uint64_t k = ctr[kFoldK], b = ctr[kFoldBlobs];
+  // every check below comes before `used` is reserved or a storage byte is written
+  if (ctr[kFoldBadLayer1])
+    return fail(e, NGPU_EINVAL,
+                "dict fold: layer_first is not 0 = first[0] <= ... <= first[%llu] = %llu at layer %llu",
+                (unsigned long long)L, (unsigned long long)n,
+                (unsigned long long)~ctr[kFoldBadLayer1]);
+  if (ctr[kFoldBadKind])
+    return fail(e, NGPU_EINVAL,
+                "dict fold: chunk %llu is no dedup result (its kind is none of NEW / INTRA / DICT; "
+                "%llu such chunks)",
+                (unsigned long long)~ctr[kFoldBadKind1], (unsigned long long)ctr[kFoldBadKind]);
+  if (ctr[kFoldBadLen])
+    return fail(e, NGPU_EINVAL,
+                "dict fold: NEW chunk %llu has length 0 or more than chunk size 0x%x (%llu such chunks)",
+                (unsigned long long)~ctr[kFoldBadLen1], e->cfg.chunk_size,
+                (unsigned long long)ctr[kFoldBadLen]);
+  if (k > n || b > L || b > k)
+    return fail(e, NGPU_EHIP, "dict fold: %llu NEW chunks in %llu layers of %llu chunks",
+                (unsigned long long)k, (unsigned long long)b, (unsigned long long)n);
+  const DictFoldPlace pr =
+      dict_fold_place_rule(base->dev.m, base->has_place, placements != nullptr, n_placements, k);
+  if (pr == kPlaceCount)
+    return fail(e, NGPU_EINVAL, "dict fold: %llu placements for %llu NEW chunks",
+                (unsigned long long)n_placements, (unsigned long long)k);
+  if (pr == kPlaceMissing)
+    return fail(e, NGPU_EINVAL, "dict fold: the base keeps compressed placements, the call gives none");
+  if (pr == kPlaceUnwanted)
+    return fail(e, NGPU_EINVAL, "dict fold: the base keeps no compressed placements, the call gives some");
+  if (blobs && n_blobs != b)
+    return fail(e, NGPU_EINVAL, "dict fold: a blob table of %u rows for %llu layers with a NEW chunk",
+                n_blobs, (unsigned long long)b);
+  uint32_t nb = 0;
+  bool with_table = false;
+  if (int r = dict_extend_check_blobs(e, base, k, (uint32_t)b, blobs && n_blobs, n_blobs, &nb, &with_table))
+    return r;
+  ngpu_dict *d = nullptr;
+  if (k == 0) {  // a handle equal to base
+    rc = dict_extend_rows(e, base, DictRowSource{}, 0, base->dev.n_blobs, base->has_place, &d);
+  } else {
+    const FoldArgs args{d_res, d_chunks, n, d_words, d_cnt, d_lfirst, L, d_rank, base->dev.n_blobs, k};
+    DictRowSource src;
+    src.write = fold_write;
+    src.arg = &args;
+    src.rows = reinterpret_cast<const DictPlace *>(placements);
+    src.stream = s;
+    src.name = "dict_fold";
+    src.pre_us = pre_ms * 1000.0f;
+    src.n = n;
+    rc = dict_extend_rows(e, base, src, k, nb, pr == kPlaceKept, &d);
+  }
+  if (rc) return rc;
+  if (with_table) {
+    d->blob_table = base->blob_table;
+    if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
+  }
+  *out = d;
+  return 0;
+}
+
+int ngpu_dict_fold(ngpu_engine *e, ngpu_dict *base, const ngpu_result *d_results,
+                   const ngpu_chunk *d_chunks, uint64_t n, const uint64_t *d_layer_first,
+                   uint64_t n_layers, const ngpu_dict_place *placements, uint64_t n_placements,
+                   const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !e || !out || (n && (!d_results || !d_chunks)) ||
+      ((uintptr_t)d_results & 15) || ((uintptr_t)d_chunks & 7) || ((uintptr_t)d_layer_first & 7) ||
+      (n_placements && !placements) || (n_blobs && !blob_table))
+    return NGPU_EINVAL;
+  return guarded([&] {
+    return dict_fold(e, base, d_results, d_chunks, n, d_layer_first, n_layers, placements,
+                     n_placements, (const uint8_t *)blob_table, n_blobs, out);
   });
 }
 

@@ -10,6 +10,8 @@
 //                        blob through the remap table, gid = the new position
 //
 // The table of the result is then built by the existing launch_dict_build.
+// Step 2 has a launcher of its own (launch_retire_scan): dict fold
+// (dict_fold.hip) scans the popcounts of its own keep words with it.
 // Roofline: HBM-bound.  Pass 1 touches every record's line for 4 bytes of it,
 // pass 3 reads the kept lines whole and writes them: 2 reads + 1 write of the
 // records against a fork's 1 + 1 (DESIGN.md §3 "Dict retire").
@@ -116,14 +118,18 @@ uint64_t dict_retire_scan_tiles(uint64_t m) {
 
 void launch_dict_keep_scan(const DictRec *rec, uint64_t m, const uint32_t *bitmap, uint32_t n_blobs,
                            uint64_t *words, uint32_t *cnt, uint64_t *sums, hipStream_t s) {
-  const uint64_t nw = (m + 63) / 64, nt = dict_retire_scan_tiles(m);
-  if (m) {
+  if (m)
     hipLaunchKernelGGL(dict_keep_words, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, rec, m,
                        bitmap, n_blobs, words, cnt);
+  launch_retire_scan(cnt, (m + 63) / 64, sums, s);
+}
+
+void launch_retire_scan(uint32_t *cnt, uint64_t nw, uint64_t *sums, hipStream_t s) {
+  const uint64_t nt = (nw + kRetireScanTile - 1) / kRetireScanTile;
+  if (nw)
     hipLaunchKernelGGL(retire_tile_sums, dim3((unsigned)nt), dim3(kTileThreads), 0, s, cnt, nw, sums);
-  }
   hipLaunchKernelGGL(retire_scan_sums, dim3(1), dim3(kTileThreads), 0, s, sums, nt);
-  if (m)
+  if (nw)
     hipLaunchKernelGGL(retire_scan_apply, dim3((unsigned)nt), dim3(kTileThreads), 0, s, cnt, nw, sums);
 }
 

@@ -437,6 +437,11 @@ void engine_unref(ngpu_engine *e) {
   }
   for (hipStream_t x : e->streams)  // every pack compute stream (+ the engine's)
     if (x != e->stream) (void)hipStreamDestroy(x);
+  if (e->fold_stream) {  // (every fold is complete when its call returns)
+    (void)hipStreamSynchronize(e->fold_stream);
+    (void)hipStreamDestroy(e->fold_stream);
+  }
+  if (e->fold_scr) (void)hipFree(e->fold_scr);
   if (e->h_results) (void)hipHostFree(e->h_results);
   if (e->host_ev) (void)hipEventDestroy(e->host_ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);

@@ -203,6 +203,14 @@ struct ngpu_engine {
   std::vector<hipStream_t> streams;  // guarded by mu
   ngpu_dict *dict = nullptr;              // default dict (one reference), may be null
   std::vector<ngpu_dict *> dict_cache;    // dicts opened by path (one reference each)
+  // dict fold / extend_device (dict.hip): their stream and the fold's scratch
+  // (keep words, prefixes, layer ranks, counters), kept between calls so that a
+  // fold allocates and frees nothing on the device (a hipFree waits for all of
+  // it).  One such call at a time per engine (fold_mu, not e->mu).
+  std::mutex fold_mu;
+  hipStream_t fold_stream = nullptr;
+  uint8_t *fold_scr = nullptr;
+  uint64_t fold_scr_cap = 0;
   // host-path device buffers
   uint8_t *d_data = nullptr;
   uint64_t d_data_cap = 0;
@@ -345,6 +353,10 @@ int dict_from_records(ngpu_engine *e, const uint8_t *recs, uint64_t m, const uin
 // blob count and *with_table whether it keeps a blob table.
 int dict_extend_check(ngpu_engine *e, const ngpu_dict *base, const uint8_t *recs, uint64_t k,
                       const uint8_t *blobs, uint32_t n_blobs, uint32_t *nb_out, bool *with_table);
+// Its half that reads no records: k more entries and nb more blobs against the
+// limits, and the blob table rule (call_has: the call passes n_blobs table rows).
+int dict_extend_check_blobs(ngpu_engine *e, const ngpu_dict *base, uint64_t k, uint32_t nb,
+                            bool call_has, uint32_t n_blobs, uint32_t *nb_out, bool *with_table);
 // A new handle of base's entries followed by k records (80 B each; blob0 is
 // added to their blob indices, gids: their global ids, null = base's count +
 // position), in place or on a new storage; place: keep their placement rows.
@@ -352,6 +364,26 @@ int dict_extend_check(ngpu_engine *e, const ngpu_dict *base, const uint8_t *recs
 int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
                         uint32_t blob0, uint32_t nb, const uint32_t *gids, bool place,
                         ngpu_dict **out);
+// Where the k new records of an extend come from.  Either 80-B records in host
+// memory (recs: uploaded through a staging buffer and unpacked, placements read
+// from them), or a kernel that writes rec[m, m + k) from what already lies in
+// HBM (write: enqueue it on s; dst = the result's rec + m; no staging buffer),
+// with the placement rows, if the result keeps any, in `rows`.  The share / fork
+// decision, the storage and the handle are the same for both (dict_extend_rows).
+struct DictRowSource {
+  const uint8_t *recs = nullptr;   // host 80-B records, or
+  const uint32_t *gids = nullptr;  //   (their global ids, null = m + position)
+  uint32_t blob0 = 0;              //   (added to their blob indices)
+  void (*write)(const DictRowSource &src, DictRec *dst, uint64_t m, hipStream_t s) = nullptr;
+  const void *arg = nullptr;       // write's own
+  const DictPlace *rows = nullptr; // device source: k placement rows (host), null = none
+  hipStream_t stream = nullptr;    // device source: the stream its inputs are ordered on
+  const char *name = "dict_extend"; // NGPU_DICT_TRACE line
+  float pre_us = 0;                // device time already spent on `stream` (the fold's keep + scan)
+  uint64_t n = 0;                  // (trace: chunks the fold read)
+};
+int dict_extend_rows(ngpu_engine *e, ngpu_dict *base, const DictRowSource &src, uint64_t k,
+                     uint32_t nb, bool place, ngpu_dict **out);
 // A storage with placement rows only (node dicts' global handles) / k more rows.
 int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
                       ngpu_dict *out);

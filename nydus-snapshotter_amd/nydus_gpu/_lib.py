@@ -86,7 +86,13 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            "ngpu_dict_extend", "ngpu_dict_extend_bootstrap", "ngpu_node_dict_extend",
            "ngpu_dict_info_get",
            # dict retire (additive in ABI 7)
-           "ngpu_dict_retire", "ngpu_node_dict_retire", "ngpu_dict_export"]
+           "ngpu_dict_retire", "ngpu_node_dict_retire", "ngpu_dict_export",
+           # dict fold (additive in ABI 7)
+           "ngpu_dict_extend_device", "ngpu_dict_fold"]
+
+# ngpu_dict_place: the compressed placement of one folded record (host rows)
+DICT_PLACE_DTYPE = np.dtype([("compressed_offset", "<u8"), ("compressed_size", "<u4"), ("flags", "<u4")])
+assert DICT_PLACE_DTYPE.itemsize == 16
 
 class NgpuDictInfo(ctypes.Structure):
     _fields_ = [("entries", ctypes.c_uint64), ("blobs", ctypes.c_uint64),
@@ -334,6 +340,8 @@ def lib():
     L.ngpu_dict_retire.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_dict_retire.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32)]
+    L.ngpu_dict_extend_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, ctypes.POINTER(vp)]
+    L.ngpu_dict_fold.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_pack_open.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
     L.ngpu_node_process_device.argtypes = [vp, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp]
     L.ngpu_node_process_step.argtypes = [vp, vp, ctypes.POINTER(NgpuNodePart), u32, u32]
@@ -823,6 +831,40 @@ class ChunkDict:
         e._check(lib().ngpu_dict_extend(e._h, self._h, _ptr(r), r.size // 80, _ptr(b),
                                         0 if b is None else b.size // 256, 0, ctypes.byref(h)),
                  "dict_extend")
+        return ChunkDict(h, e)
+
+    def extend_device(self, d_digests: int, d_usize: int, d_blob: int, d_index: int, n: int,
+                      n_blobs: int, d_uoff: int = 0) -> "ChunkDict":
+        """ngpu_dict_extend_device: extend() from device arrays (those of
+        Engine.dict_create_device; the blob indices count from this dict's blob
+        count, n_blobs is the caller's word for how many blobs the rows bring)."""
+        e = self._engine()
+        h = ctypes.c_void_p()
+        e._check(lib().ngpu_dict_extend_device(
+            e._h, self._h, e._vp(d_digests), e._vp(d_usize), e._vp(d_blob), e._vp(d_index),
+            e._vp(d_uoff), n, n_blobs, 0, ctypes.byref(h)), "dict_extend_device")
+        return ChunkDict(h, e)
+
+    def fold(self, d_results: int, d_chunks: int, n: int, d_layer_first: int = 0, n_layers: int = 1,
+             placements=None, blobs=None) -> "ChunkDict":
+        """ngpu_dict_fold: a new dict of this one's entries followed by one record
+        per NEW chunk of a dedup call's device result table (d_results / d_chunks:
+        n RESULT_DTYPE / CHUNK_DTYPE rows in HBM; d_layer_first: n_layers + 1
+        device u64 cuts, 0 = one layer).  Every layer with a NEW chunk is one new
+        blob.  placements: DICT_PLACE_DTYPE rows, one per NEW chunk in order;
+        blobs: the new blobs' 256-B records.  The stream that wrote the results
+        must have been synchronised.  This handle stays as it is."""
+        e = self._engine()
+        p = None if placements is None else np.ascontiguousarray(placements, dtype=DICT_PLACE_DTYPE)
+        b = None if blobs is None or not len(blobs) else np.ascontiguousarray(blobs).view(np.uint8).reshape(-1)
+        # (an empty placement list is still "placements given": a non-NULL pointer)
+        room = p if p is None or len(p) else np.zeros(1, DICT_PLACE_DTYPE)
+        pp = None if room is None else ctypes.c_void_p(room.ctypes.data)
+        h = ctypes.c_void_p()
+        e._check(lib().ngpu_dict_fold(e._h, self._h, e._vp(d_results), e._vp(d_chunks), n,
+                                      e._vp(d_layer_first), n_layers, pp, 0 if p is None else len(p),
+                                      _ptr(b), 0 if b is None else b.size // 256, 0, ctypes.byref(h)),
+                 "dict_fold")
         return ChunkDict(h, e)
 
     def extend_bootstrap(self, path: str) -> "ChunkDict":
