@@ -698,6 +698,58 @@ int ngpu_node_dict_open(ngpu_node *node, const char *path, uint32_t mode, ngpu_d
  * in place or copies by its own fill.  A plain dict here is NGPU_EINVAL. */
 int ngpu_node_dict_extend(ngpu_node *node, ngpu_dict *base, const void *records, uint64_t n,
                           const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
+/* ---- node dict fold: grow a node dict from a step's results (additive in ABI 7) ----
+ * ngpu_dict_fold for node dicts: part i is the result table of a dedup /
+ * process / step call on node device i (ngpu_node_process_step,
+ * ngpu_node_process_device), with its descriptors and layer cuts as
+ * ngpu_dict_fold takes them; a part with n == 0 takes part with nothing.  out
+ * answers every probe, Pack, Check, stats field and (replicated dicts) export
+ * exactly as ngpu_node_dict_extend over the concatenated host rows: part 0's fold
+ * rows, then part 1's, ..., each part's rows as ngpu_dict_fold defines them (one
+ * per kind == NGPU_NEW chunk, in chunk order), with blob ranks that run on across
+ * the parts: the blob rank of layer l of part i is the number of layers with a
+ * NEW chunk in the parts before i plus those before l in part i.  placements
+ * and blob_table rows are given in that same global order (k = all parts' NEW
+ * chunks, b = all parts' layers with one).
+ *
+ * First entry wins: base over new rows, and a digest NEW in two parts keeps the
+ * lower part's row.  Handles older than out stay blind to an in-place append;
+ * each part appends in place or copies by its own fill; the exchange mode and
+ * replicated / partitioned are base's.  k == 0 over all parts returns a handle
+ * equal to base.
+ *
+ * Every refusal of ngpu_dict_fold applies to each part (the message names the
+ * part and the chunk or layer), its placement and blob-table rules to k and b.
+ * Also NGPU_EINVAL: n_parts != ngpu_node_size(node); flags != 0; a plain dict or
+ * a dict of another node (ngpu_dict_fold keeps refusing node dicts).  All
+ * refusals are decided after the counts of all parts are back -- one small copy
+ * per part, all parts enqueued before the first wait, the call's only mid-way
+ * one -- and before any part's record slot is reserved or a storage byte is
+ * written: a refused call leaves every part as it was.  A failure after that
+ * point behaves as in ngpu_node_dict_extend: *out is NULL, base stays usable,
+ * id ranges may be left dead.
+ *
+ * The rows never pass through the host: each part's rows are written into a
+ * staging area on its own device with their final global ids and blobs, a
+ * partitioned dict splits them by owner there (a stable split: an owner's rows
+ * stay in global table order), and every part then copies the rows it keeps
+ * with DMA copies (hipMemcpyPeerAsync between devices), no peer stores from
+ * kernels.  The device work runs on each engine's own fold stream, outside the
+ * engine locks, and is complete on return; it does not wait for the caller's
+ * streams, so the streams that wrote the results must have been synchronised.
+ * Once warm, an in-place fold allocates and frees no device memory.
+ * UNVERIFIED ON DISTINCT GPUs, as the node exchange above: every test so far
+ * lists one GPU several times, so the peer copies stay inside one HBM. */
+typedef struct {
+  const ngpu_result *d_results;  /* on node device i: a dedup / process / step call's result table */
+  const ngpu_chunk *d_chunks;    /* its n descriptors */
+  uint64_t n;
+  const uint64_t *d_layer_first; /* n_layers + 1 cuts on that device; NULL or n_layers <= 1: one layer */
+  uint64_t n_layers;
+} ngpu_node_fold_part;           /* 40 bytes */
+int ngpu_node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *parts,
+                        uint32_t n_parts, const ngpu_dict_place *placements, uint64_t n_placements,
+                        const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
 /* ngpu_dict_retire for node dicts.  A replicated dict retires every replica
  * with the same result (global id = position) and the node handle's placement
  * rows follow.  A partitioned dict returns NGPU_EUNSUPP: its parts' new global

@@ -344,6 +344,19 @@ void launch_dict_pack_at(const uint8_t *digests, const uint32_t *usize, const ui
                          const uint32_t *index, const uint64_t *uoff, uint64_t n, uint32_t blob0,
                          uint32_t gid0, DictRec *out, hipStream_t s);
 
+// node_fold.hip (node dict fold, node.hip).  The NEW chunks of res[0, n) per
+// owner part (owner_of over digest word 0, W <= 64) added to cnt[0, W), which the
+// caller zeroed on s.
+void launch_fold_owner_counts(const ngpu_result *res, uint64_t n, uint32_t W, uint32_t *cnt,
+                              hipStream_t s);
+// The stable split of rows[0, k) by owner into out[0, k): owner 0's rows first,
+// each owner's in their order in `rows`.  Five launches whatever W is.  cnt: W x
+// node_split_tiles(k) u32 (left holding every tile's start per owner); sums:
+// (W x tiles + 255) / 256 + 1 u64.
+uint64_t node_split_tiles(uint64_t k);
+void launch_node_split(const DictRec *rows, uint64_t k, uint32_t W, uint32_t *cnt, uint64_t *sums,
+                       DictRec *out, hipStream_t s);
+
 // Device workspace, grown on demand and owned by the engine.
 struct Workspace {
   uint64_t *groups = nullptr;     // n+1: leaf groups per chunk -> exclusive scan

@@ -497,8 +497,9 @@ int dict_extend_rows(ngpu_engine *e, ngpu_dict *base, const DictRowSource &src, 
   return 0;
 }
 
-int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
-                      ngpu_dict *out) {
+// recs: 80-B records, or (null) rows: their placement rows.
+static int place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, const DictPlace *rows,
+                        uint64_t k, ngpu_dict *out) {
   const uint64_t m = base ? base->dev.m : 0;
   DictStorage *st = base ? base->st : nullptr;
   const bool base_rows = base && base->has_place && st && st->place;
@@ -528,13 +529,24 @@ int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint
     }
     if (base_rows) memcpy(st->place, base->st->place, m * sizeof(DictPlace));
   }
-  for (uint64_t i = 0; i < k; ++i) {
+  if (!recs && k) memcpy(st->place + m, rows, k * sizeof(DictPlace));
+  for (uint64_t i = 0; recs && i < k; ++i) {
     const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
     st->place[m + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
   }
   out->st = st;
   out->has_place = m + k != 0;
   return 0;
+}
+
+int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
+                      ngpu_dict *out) {
+  return place_extend(e, base, recs, nullptr, k, out);
+}
+
+int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const DictPlace *rows, uint64_t k,
+                      ngpu_dict *out) {
+  return place_extend(e, base, nullptr, rows, k, out);
 }
 
 // ---- dict retire ---------------------------------------------------------------
@@ -1123,8 +1135,10 @@ static_assert(sizeof(ngpu_dict_place) == sizeof(DictPlace) &&
                   offsetof(ngpu_dict_place, flags) == offsetof(DictPlace, flags),
               "ngpu_dict_place is a DictPlace");
 
+}  // extern "C"
+
 // e->fold_mu held: the fold stream, and at least `bytes` of scratch.
-static int fold_lane(ngpu_engine *e, uint64_t bytes) {
+int ngpu::fold_lane(ngpu_engine *e, uint64_t bytes) {
   if (!e->fold_stream &&
       hipStreamCreateWithFlags(&e->fold_stream, hipStreamNonBlocking) != hipSuccess) {
     (void)hipGetLastError();
@@ -1146,6 +1160,8 @@ static int fold_lane(ngpu_engine *e, uint64_t bytes) {
   }
   return 0;
 }
+
+extern "C" {
 
 namespace {
 struct FoldArgs {

@@ -442,6 +442,9 @@ void engine_unref(ngpu_engine *e) {
     (void)hipStreamDestroy(e->fold_stream);
   }
   if (e->fold_scr) (void)hipFree(e->fold_scr);
+  if (e->fold_rows) (void)hipFree(e->fold_rows);
+  if (e->fold_h) (void)hipHostFree(e->fold_h);
+  if (e->fold_ev) (void)hipEventDestroy(e->fold_ev);
   if (e->h_results) (void)hipHostFree(e->h_results);
   if (e->host_ev) (void)hipEventDestroy(e->host_ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);

@@ -211,6 +211,13 @@ struct ngpu_engine {
   hipStream_t fold_stream = nullptr;
   uint8_t *fold_scr = nullptr;
   uint64_t fold_scr_cap = 0;
+  // node dict fold (node.hip), kept in the same way (fold_mu): the part's staged
+  // rows (+ their split by owner and its counts), the pinned landing of its
+  // counters, and the event that says its rows are staged
+  uint8_t *fold_rows = nullptr;
+  uint64_t fold_rows_cap = 0;
+  uint64_t *fold_h = nullptr;
+  hipEvent_t fold_ev = nullptr;
   // host-path device buffers
   uint8_t *d_data = nullptr;
   uint64_t d_data_cap = 0;
@@ -387,6 +394,12 @@ int dict_extend_rows(ngpu_engine *e, ngpu_dict *base, const DictRowSource &src, 
 // A storage with placement rows only (node dicts' global handles) / k more rows.
 int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t k,
                       ngpu_dict *out);
+// The same with the k rows given as placement rows (node dict fold).
+int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const DictPlace *rows, uint64_t k,
+                      ngpu_dict *out);
+// e->fold_mu held: the engine's fold stream, and at least `bytes` of fold_scr
+// (dict.hip; grown only while nothing of an earlier fold still runs).
+int fold_lane(ngpu_engine *e, uint64_t bytes);
 void storage_unref(DictStorage *st);
 // Dict retire (dict.hip): a new handle, on a storage of its own, of base's own
 // records whose blob bitmap bit is clear, blob indices through remap (both

@@ -40,6 +40,7 @@
 #include "a2a_plan.hpp"
 #include "dict_retire_plan.hpp"
 #include "engine_internal.hpp"
+#include "node_fold_plan.hpp"
 
 using namespace ngpu;
 
@@ -452,6 +453,302 @@ int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, ui
     return rc;
   }
   d->blob_table = dict_retire_blob_table(base->blob_table, plan.remap);
+  *out = d;
+  return 0;
+}
+
+// ---- node dict fold ------------------------------------------------------------
+// ngpu_dict_fold for node dicts: every part's result table becomes dict rows on
+// its own device, and the rows reach the parts that keep them by DMA copies.
+// Per part i, on engine i's fold stream and kept scratch (fold_mu, taken in index
+// order):
+//   a. dict fold's keep words, scan and layer ranks (launch_fold_keep_scan,
+//      unchanged) and, for a partitioned base, its NEW chunks per owner
+//      (fold_owner_counts); one 320-B copy into pinned memory brings back k_i,
+//      b_i, the refusal counters and the W owner counts.  All W parts are
+//      enqueued before the first wait, the call's only mid-way one.
+//   b. the host plan (node_fold_plan.hpp): offsets, totals, segments, refusals --
+//      all of them before any `used` is reserved or a storage byte is written.
+//   c. launch_fold_scatter writes part i's rows into a staging area on device i
+//      with their final global ids and blobs (sized for k = n before a., so the
+//      keep words are never freed under the call).
+//   d. partitioned: the stable split of the staged rows by owner (node_fold.hip).
+//   e. each part's extend through dict_extend_rows: its write waits for the
+//      source parts' "staged" events and copies a replica all W staging areas, a
+//      partition its W segments, in source order (hipMemcpyAsync for its own,
+//      hipMemcpyPeerAsync for the others); the insert or build follows unchanged.
+//   f. the global handle's placement rows and blob table, as node_dict_extend.
+struct NodeFoldRows {
+  uint8_t *scr = nullptr;  // engine i's fold_scr
+  uint64_t o_sums = 0, o_ctr = 0, o_cnt = 0, o_rank = 0;
+  DictRec *staged = nullptr, *split = nullptr;
+  uint32_t *tcnt = nullptr;
+  uint64_t *tsums = nullptr;
+};
+constexpr uint64_t kNodeFoldCtrBytes = 8 * kFoldCtrWords + 4 * kNodeFoldMaxParts;  // counters + owner counts
+
+struct NodeFoldCopy {
+  ngpu_node *node;
+  const NodeFoldPlan *plan;
+  const std::vector<NodeFoldRows> *rows;
+  const uint32_t *c;  // W x W owner counts, null: replicated
+  uint32_t W, o;
+};
+void node_fold_write(const DictRowSource &src, DictRec *dst, uint64_t, hipStream_t s) {
+  const NodeFoldCopy &a = *static_cast<const NodeFoldCopy *>(src.arg);
+  const uint32_t W = a.W, o = a.o;
+  for (uint32_t i = 0; i < W; ++i) {
+    const uint64_t cnt = a.c ? a.c[(size_t)i * W + o] : a.plan->off[i + 1] - a.plan->off[i];
+    if (!cnt) continue;
+    const NodeFoldRows &r = (*a.rows)[i];
+    const DictRec *from = a.c ? r.split + a.plan->src[(size_t)i * W + o] : r.staged;
+    DictRec *to = dst + (a.c ? a.plan->dst[(size_t)i * W + o] : a.plan->off[i]);
+    if (i == o) {  // staged on this very stream
+      (void)hipMemcpyAsync(to, from, cnt * sizeof(DictRec), hipMemcpyDeviceToDevice, s);
+    } else if (hipStreamWaitEvent(s, a.node->eng[i]->fold_ev, 0) == hipSuccess) {
+      (void)hipMemcpyPeerAsync(to, a.node->dev[o], from, a.node->dev[i], cnt * sizeof(DictRec), s);
+    }
+  }
+}
+
+// e->fold_mu held: at least `bytes` of fold_rows, the pinned counters and the event.
+int node_fold_lane(ngpu_engine *e, uint64_t bytes) {
+  if (!e->fold_h && hipHostMalloc((void **)&e->fold_h, 512) != hipSuccess) {
+    (void)hipGetLastError();
+    e->fold_h = nullptr;
+    return fail(e, NGPU_ENOMEM, "node dict fold: pinned counters");
+  }
+  if (!e->fold_ev && hipEventCreateWithFlags(&e->fold_ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    e->fold_ev = nullptr;
+    return fail(e, NGPU_EHIP, "node dict fold: event on device %d", e->device);
+  }
+  if (bytes > e->fold_rows_cap) {
+    // (nothing of an earlier fold still runs: each is complete when it returns)
+    if (e->fold_rows) (void)hipFree(e->fold_rows);
+    e->fold_rows = nullptr;
+    e->fold_rows_cap = 0;
+    const uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 1u << 16);
+    if (hipMalloc((void **)&e->fold_rows, want) != hipSuccess) {
+      (void)hipGetLastError();
+      e->fold_rows = nullptr;
+      return fail(e, NGPU_ENOMEM, "node dict fold: staging allocation failed");
+    }
+    e->fold_rows_cap = want;
+  }
+  return 0;
+}
+
+int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *pt, uint32_t np,
+                   const ngpu_dict_place *placements, uint64_t n_placements, const uint8_t *blobs,
+                   uint32_t n_blobs, ngpu_dict **out) {
+  ngpu_engine *e0 = node->eng[0];
+  const uint32_t W = (uint32_t)node->eng.size();
+  if (np != W)
+    return fail(e0, NGPU_EINVAL, "node dict fold: %u parts for a node of %u devices", np, W);
+  if (base->parts.empty())
+    return fail(e0, NGPU_EINVAL, "node dict fold: not a node dict (ngpu_dict_fold takes it)");
+  if (base->parts.size() != W) return fail(e0, NGPU_EINVAL, "node dict fold: dict of another node");
+  for (uint32_t o = 0; o < W; ++o)
+    if (base->parts[o]->device != node->eng[o]->device)
+      return fail(e0, NGPU_EINVAL, "node dict fold: dict of another node");
+  if (int rc = dict_check(e0, base)) return rc;
+  std::vector<uint64_t> L(W);
+  std::vector<const uint64_t *> lfirst(W);
+  for (uint32_t i = 0; i < W; ++i) {
+    const ngpu_node_fold_part &p = pt[i];
+    if ((p.n && (!p.d_results || !p.d_chunks)) || ((uintptr_t)p.d_results & 15) ||
+        ((uintptr_t)p.d_chunks & 7) || ((uintptr_t)p.d_layer_first & 7))
+      return fail(e0, NGPU_EINVAL, "node dict fold: part %u: missing or misaligned tables", i);
+    if (p.n >= kDictMaxEntries || p.n_layers >= kDictMaxEntries)
+      return fail(e0, NGPU_EINVAL, "node dict fold: part %u: %llu chunks in %llu layers in one call", i,
+                  (unsigned long long)p.n, (unsigned long long)p.n_layers);
+    const bool one = !p.d_layer_first || p.n_layers <= 1;  // one layer of n chunks
+    lfirst[i] = one ? nullptr : p.d_layer_first;
+    L[i] = one ? 1 : p.n_layers;
+  }
+  const bool split = !base->replicated;
+  const uint64_t m = base->dev.m;
+  std::vector<std::unique_lock<std::mutex>> lanes;
+  for (uint32_t i = 0; i < W; ++i) lanes.emplace_back(node->eng[i]->fold_mu);
+
+  // a. counts: every part enqueued, then waited for
+  std::vector<NodeFoldRows> rows(W);
+  int rc = 0;
+  for (uint32_t i = 0; i < W && !rc; ++i) {
+    ngpu_engine *e = node->eng[i];
+    const ngpu_node_fold_part &p = pt[i];
+    NodeFoldRows &r = rows[i];
+    DeviceGuard dg(e->device);
+    const uint64_t n = p.n, nw = (n + 63) / 64, nt = dict_retire_scan_tiles(n);
+    r.o_sums = 8 * nw;
+    r.o_ctr = r.o_sums + 8 * (nt + 1);
+    r.o_cnt = r.o_ctr + kNodeFoldCtrBytes;
+    r.o_rank = r.o_cnt + 4 * nw;
+    // the staging areas for the worst case k = n, before the keep words exist
+    const uint64_t tw = (uint64_t)W * node_split_tiles(n);
+    const uint64_t o_split = n * sizeof(DictRec), o_tcnt = 2 * o_split,
+                   o_tsums = (o_tcnt + 4 * tw + 7) & ~7ull,
+                   bytes = split ? o_tsums + 8 * ((tw + kRetireScanTile - 1) / kRetireScanTile + 1) : o_split;
+    if ((rc = fold_lane(e, r.o_rank + 4 * L[i])) || (rc = node_fold_lane(e, bytes))) {
+      rc = fail(e0, rc, "%s", ngpu_last_error(e));
+      break;
+    }
+    r.scr = e->fold_scr;
+    r.staged = (DictRec *)e->fold_rows;
+    if (split) {
+      r.split = (DictRec *)(e->fold_rows + o_split);
+      r.tcnt = (uint32_t *)(e->fold_rows + o_tcnt);
+      r.tsums = (uint64_t *)(e->fold_rows + o_tsums);
+    }
+    const hipStream_t s = e->fold_stream;
+    uint64_t *d_ctr = (uint64_t *)(r.scr + r.o_ctr);
+    bool ok = hipMemsetAsync(d_ctr, 0, kNodeFoldCtrBytes, s) == hipSuccess;
+    if (ok) {
+      launch_fold_keep_scan(p.d_results, p.d_chunks, n, e->cfg.chunk_size, lfirst[i], L[i],
+                            (uint64_t *)r.scr, (uint32_t *)(r.scr + r.o_cnt),
+                            (uint64_t *)(r.scr + r.o_sums), (uint32_t *)(r.scr + r.o_rank), d_ctr, s);
+      if (split) launch_fold_owner_counts(p.d_results, n, W, (uint32_t *)(d_ctr + kFoldCtrWords), s);
+      ok = hipGetLastError() == hipSuccess &&
+           hipMemcpyAsync(e->fold_h, d_ctr, kNodeFoldCtrBytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+    }
+    if (!ok) rc = fail(e0, NGPU_EHIP, "node dict fold: part %u: keep scan failed", i);
+  }
+  for (uint32_t i = 0; i < W; ++i) {  // (every stream is waited for, whatever another one said)
+    DeviceGuard dg(node->dev[i]);
+    const hipStream_t s = node->eng[i]->fold_stream;
+    if (s && hipStreamSynchronize(s) != hipSuccess && !rc)
+      rc = fail(e0, NGPU_EHIP, "node dict fold: part %u: keep scan failed", i);
+  }
+  if (rc) return rc;
+
+  // b. the plan; every refusal comes before `used` is reserved or a storage byte is written
+  std::vector<uint64_t> k(W), b(W);
+  std::vector<uint32_t> c(split ? (size_t)W * W : 0);
+  for (uint32_t i = 0; i < W; ++i) {
+    const uint64_t *ctr = node->eng[i]->fold_h;
+    const uint64_t n = pt[i].n;
+    if (ctr[kFoldBadLayer1])
+      return fail(e0, NGPU_EINVAL,
+                  "node dict fold: part %u: layer_first is not 0 = first[0] <= ... <= first[%llu] = %llu "
+                  "at layer %llu",
+                  i, (unsigned long long)L[i], (unsigned long long)n,
+                  (unsigned long long)~ctr[kFoldBadLayer1]);
+    if (ctr[kFoldBadKind])
+      return fail(e0, NGPU_EINVAL,
+                  "node dict fold: part %u: chunk %llu is no dedup result (its kind is none of NEW / "
+                  "INTRA / DICT; %llu such chunks)",
+                  i, (unsigned long long)~ctr[kFoldBadKind1], (unsigned long long)ctr[kFoldBadKind]);
+    if (ctr[kFoldBadLen])
+      return fail(e0, NGPU_EINVAL,
+                  "node dict fold: part %u: NEW chunk %llu has length 0 or more than chunk size 0x%x "
+                  "(%llu such chunks)",
+                  i, (unsigned long long)~ctr[kFoldBadLen1], e0->cfg.chunk_size,
+                  (unsigned long long)ctr[kFoldBadLen]);
+    k[i] = ctr[kFoldK];
+    b[i] = ctr[kFoldBlobs];
+    if (k[i] > n || b[i] > L[i] || b[i] > k[i])
+      return fail(e0, NGPU_EHIP, "node dict fold: part %u: %llu NEW chunks in %llu layers of %llu chunks",
+                  i, (unsigned long long)k[i], (unsigned long long)b[i], (unsigned long long)n);
+    if (split) memcpy(&c[(size_t)i * W], ctr + kFoldCtrWords, 4 * W);
+  }
+  const NodeFoldPlan plan = node_fold_plan(W, k.data(), b.data(), split ? c.data() : nullptr);
+  if (!plan.ok)
+    return fail(e0, NGPU_EHIP, "node dict fold: part %u: its owner counts do not add up to its %llu NEW chunks",
+                plan.bad, (unsigned long long)k[plan.bad]);
+  const uint64_t K = plan.K;
+  const bool call_table = blobs && n_blobs;
+  const DictFoldPlace pr =
+      node_fold_place_rule(m, base->has_place, placements != nullptr, n_placements, plan);
+  if (pr == kPlaceCount)
+    return fail(e0, NGPU_EINVAL, "node dict fold: %llu placements for %llu NEW chunks",
+                (unsigned long long)n_placements, (unsigned long long)K);
+  if (pr == kPlaceMissing)
+    return fail(e0, NGPU_EINVAL, "node dict fold: the base keeps compressed placements, the call gives none");
+  if (pr == kPlaceUnwanted)
+    return fail(e0, NGPU_EINVAL, "node dict fold: the base keeps no compressed placements, the call gives some");
+  if (!node_fold_table_rows_ok(blobs != nullptr, n_blobs, plan))
+    return fail(e0, NGPU_EINVAL, "node dict fold: a blob table of %u rows for %llu layers with a NEW chunk",
+                n_blobs, (unsigned long long)plan.B);
+  // (over the untruncated sums: dict_extend_check_blobs below takes a 32-bit blob count)
+  const NodeFoldLimit lim = node_fold_limits(m, base->dev.n_blobs, K, plan.B);
+  if (lim == kNodeFoldEntries)
+    return fail(e0, NGPU_EINVAL, "chunk dict too large (%llu entries)", (unsigned long long)(m + K));
+  if (lim == kNodeFoldBlobs)
+    return fail(e0, NGPU_EINVAL, "chunk dict blob index %llu too large",
+                (unsigned long long)(base->dev.n_blobs + plan.B - 1));
+  uint32_t nb = 0;
+  bool with_table = false;
+  if (int r = dict_extend_check_blobs(e0, base, K, (uint32_t)plan.B, call_table, n_blobs, &nb, &with_table))
+    return r;
+
+  // c, d. the rows, staged with their final ids and blobs (and split by owner)
+  for (uint32_t i = 0; i < W; ++i) {
+    if (!k[i]) continue;
+    ngpu_engine *e = node->eng[i];
+    const ngpu_node_fold_part &p = pt[i];
+    const NodeFoldRows &r = rows[i];
+    DeviceGuard dg(e->device);
+    const hipStream_t s = e->fold_stream;
+    launch_fold_scatter(p.d_results, p.d_chunks, p.n, (const uint64_t *)r.scr,
+                        (const uint32_t *)(r.scr + r.o_cnt), lfirst[i], L[i],
+                        (const uint32_t *)(r.scr + r.o_rank), base->dev.n_blobs + (uint32_t)plan.boff[i],
+                        (uint32_t)(m + plan.off[i]), r.staged, k[i], s);
+    if (split) launch_node_split(r.staged, k[i], W, r.tcnt, r.tsums, r.split, s);
+    if (hipGetLastError() != hipSuccess || hipEventRecord(e->fold_ev, s) != hipSuccess) {
+      rc = fail(e0, NGPU_EHIP, "node dict fold: part %u: staging its rows failed", i);
+      break;
+    }
+  }
+  auto quiesce = [&] {  // nothing of this call still reads a scratch when it returns
+    for (uint32_t i = 0; i < W; ++i) {
+      DeviceGuard dg(node->dev[i]);
+      (void)hipStreamSynchronize(node->eng[i]->fold_stream);
+    }
+  };
+  if (rc) {
+    quiesce();
+    return rc;
+  }
+
+  // e, f. the handle: placement rows, every part's extend, the blob table
+  ngpu_dict *d = new ngpu_dict();
+  d->device = base->device;
+  d->digester = base->digester;
+  d->chunk_size = base->chunk_size;
+  d->replicated = base->replicated;
+  d->routed = base->routed;
+  d->dev.m = m + K;
+  d->dev.n_blobs = nb;
+  if (pr == kPlaceKept || K == 0)
+    rc = dict_place_extend(e0, base, reinterpret_cast<const DictPlace *>(placements), K, d);
+  for (uint32_t o = 0; o < W && !rc; ++o) {
+    ngpu_dict *p = nullptr;
+    const uint64_t pk = split ? plan.total[o] : K;
+    const NodeFoldCopy args{node, &plan, &rows, split ? c.data() : nullptr, W, o};
+    DictRowSource src;
+    if (pk) {
+      src.write = node_fold_write;
+      src.arg = &args;
+      src.stream = node->eng[o]->fold_stream;
+      src.name = "node_dict_fold";
+      src.n = pt[o].n;
+    }
+    if ((rc = dict_extend_rows(node->eng[o], base->parts[o], src, pk, nb, false, &p))) {
+      rc = fail(e0, rc, "%s", ngpu_last_error(node->eng[o]));
+      break;
+    }
+    d->parts.push_back(p);
+  }
+  quiesce();
+  if (rc) {
+    dict_unref(d);
+    return rc;
+  }
+  if (with_table) {
+    d->blob_table = base->blob_table;
+    if (call_table) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
+  }
   *out = d;
   return 0;
 }
@@ -873,6 +1170,21 @@ int ngpu_node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blob
   if (out) *out = nullptr;
   if (!base || flags || !node || !out || (n && !blobs)) return NGPU_EINVAL;
   return guarded([&] { return node_dict_retire(node, base, blobs, n, out); });
+}
+
+static_assert(sizeof(ngpu_node_fold_part) == 40, "ngpu_node_fold_part is 40 bytes");
+
+int ngpu_node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *parts,
+                        uint32_t n_parts, const ngpu_dict_place *placements, uint64_t n_placements,
+                        const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !node || !out || !parts || (n_placements && !placements) ||
+      (n_blobs && !blob_table))
+    return NGPU_EINVAL;
+  return guarded([&] {
+    return node_dict_fold(node, base, parts, n_parts, placements, n_placements,
+                          (const uint8_t *)blob_table, n_blobs, out);
+  });
 }
 
 int ngpu_node_dict_open(ngpu_node *node, const char *path, uint32_t mode, ngpu_dict **out) {

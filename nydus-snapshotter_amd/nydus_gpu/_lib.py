@@ -88,7 +88,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # dict retire (additive in ABI 7)
            "ngpu_dict_retire", "ngpu_node_dict_retire", "ngpu_dict_export",
            # dict fold (additive in ABI 7)
-           "ngpu_dict_extend_device", "ngpu_dict_fold"]
+           "ngpu_dict_extend_device", "ngpu_dict_fold",
+           # node dict fold (additive in ABI 7)
+           "ngpu_node_dict_fold"]
 
 # ngpu_dict_place: the compressed placement of one folded record (host rows)
 DICT_PLACE_DTYPE = np.dtype([("compressed_offset", "<u8"), ("compressed_size", "<u4"), ("flags", "<u4")])
@@ -342,6 +344,7 @@ def lib():
     L.ngpu_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32)]
     L.ngpu_dict_extend_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_dict_fold.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
+    L.ngpu_node_dict_fold.argtypes = [vp, vp, vp, u32, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_pack_open.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
     L.ngpu_node_process_device.argtypes = [vp, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp]
     L.ngpu_node_process_step.argtypes = [vp, vp, ctypes.POINTER(NgpuNodePart), u32, u32]
@@ -1445,6 +1448,14 @@ class NgpuNodePart(ctypes.Structure):
                 ("n_layers", ctypes.c_uint64), ("d_stats", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
 
 
+class NgpuNodeFoldPart(ctypes.Structure):
+    """ngpu_node_fold_part: one device's result table of a node dict fold."""
+    _fields_ = [("d_results", ctypes.c_void_p), ("d_chunks", ctypes.c_void_p), ("n", ctypes.c_uint64),
+                ("d_layer_first", ctypes.c_void_p), ("n_layers", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(NgpuNodeFoldPart) == 40
+
 NODE_STEP_RCCL = 1  # ngpu_node_process_step: the all-to-alls are RCCL ncclAllToAllv
 NODE_DICT_PARTITION, NODE_DICT_REPLICATE = 0, 1
 NODE_EXCHANGE_COPY = 0x100  # | PARTITION: the broadcast + DMA exchange (the default since ABI 7)
@@ -1525,6 +1536,34 @@ class Node:
         self._err(lib().ngpu_node_dict_extend(self._h, base._h, _ptr(r), r.size // 80, _ptr(b),
                                               0 if b is None else b.size // 256, 0, ctypes.byref(h)),
                   "node_dict_extend")
+        return ChunkDict(h)
+
+    def dict_fold(self, base: ChunkDict, parts, placements=None, blobs=None) -> ChunkDict:
+        """ngpu_node_dict_fold: a new node dict of base's entries followed by one
+        record per NEW chunk of every part's device result table, part 0's first.
+        parts: one dict per node device, as process_step takes them, with keys
+        d_results (or d_out), d_chunks, n and optionally d_layer_first, n_layers
+        (ints: device pointers on that device).  Every layer with a NEW chunk is
+        one new blob, counted across the parts.  placements: DICT_PLACE_DTYPE
+        rows, one per NEW chunk in that global order; blobs: the new blobs'
+        256-B records.  The streams that wrote the results must have been
+        synchronised."""
+        arr = (NgpuNodeFoldPart * max(len(parts), 1))()
+        for i, p in enumerate(parts):
+            arr[i] = NgpuNodeFoldPart(p.get("d_results", p.get("d_out", 0)) or None,
+                                      p.get("d_chunks", 0) or None, p.get("n", 0),
+                                      p.get("d_layer_first", 0) or None,
+                                      p.get("n_layers", 1 if p.get("d_layer_first") else 0))
+        pl = None if placements is None else np.ascontiguousarray(placements, dtype=DICT_PLACE_DTYPE)
+        b = None if blobs is None or not len(blobs) else np.ascontiguousarray(blobs).view(np.uint8).reshape(-1)
+        # (an empty placement list is still "placements given": a non-NULL pointer)
+        room = pl if pl is None or len(pl) else np.zeros(1, DICT_PLACE_DTYPE)
+        pp = None if room is None else ctypes.c_void_p(room.ctypes.data)
+        h = ctypes.c_void_p()
+        self._err(lib().ngpu_node_dict_fold(self._h, base._h, arr, len(parts), pp,
+                                            0 if pl is None else len(pl), _ptr(b),
+                                            0 if b is None else b.size // 256, 0, ctypes.byref(h)),
+                  "node_dict_fold")
         return ChunkDict(h)
 
     def dict_export(self, d: ChunkDict):
