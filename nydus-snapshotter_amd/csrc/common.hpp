@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dict_fold_plan.hpp"
 #include "dict_hash.hpp"
 #include "nydus_gpu.h"
 
@@ -289,17 +290,17 @@ void launch_hits_scatter(const ngpu_dict_hit *routed, const uint32_t *rows, uint
 void launch_dict_unpack(const uint8_t *recs, uint64_t n, const uint32_t *gids, uint32_t gid0,
                         DictRec *out, hipStream_t s, uint32_t blob0 = 0);
 // Device SoA arrays -> dict records (index / uoff may be null: 0), gid =
-// gid[i] (null: i).
+// gid[i] (null: gid0 + i); blob0 is added to every blob index.
 void launch_dict_pack(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,
                       const uint32_t *index, const uint64_t *uoff, const uint32_t *gid, uint64_t n,
-                      DictRec *out, hipStream_t s);
+                      uint32_t blob0, uint32_t gid0, DictRec *out, hipStream_t s);
 // dict_retire.hip (dict retire).  Launches 1-2: keep word and survivor count
 // per 64 records of rec[0, m) (a record stays unless bit rec.blob of bitmap is
 // set), then cnt -> exclusive prefixes in place.  words / cnt: (m + 63) / 64
 // entries; sums: dict_retire_scan_tiles(m) + 1 words, the last one receives the
-// number of survivors.  One scan tile is kRetireScanTile keep words.
-constexpr uint64_t kRetireScanTile = kTileThreads;  // words: 16,384 records
-uint64_t dict_retire_scan_tiles(uint64_t m);
+// number of survivors.  One scan tile is kRetireScanTile keep words
+// (dict_retire_plan.hpp), a workgroup of the scan.
+static_assert(kRetireScanTile == kTileThreads, "a scan tile is one workgroup");
 void launch_dict_keep_scan(const DictRec *rec, uint64_t m, const uint32_t *bitmap, uint32_t n_blobs,
                            uint64_t *words, uint32_t *cnt, uint64_t *sums, hipStream_t s);
 // Launch 3: the survivors to out[0, n_out) in order, blob = remap[blob], gid =
@@ -312,16 +313,8 @@ void launch_dict_compact(const DictRec *rec, uint64_t m, const uint64_t *words,
 // kRetireScanTile); sums: nt + 1 words.
 void launch_retire_scan(uint32_t *cnt, uint64_t nw, uint64_t *sums, hipStream_t s);
 
-// dict_fold.hip (dict fold, dict.hip).  ctr: kFoldCtrWords u64, zeroed on s by
-// the caller before launch_fold_keep_scan.
-constexpr int kFoldK = 0;         // NEW chunks of the call
-constexpr int kFoldBlobs = 1;     // layers with a NEW chunk
-constexpr int kFoldBadKind = 2;   // chunks whose kind is none of NEW / INTRA / DICT
-constexpr int kFoldBadKind1 = 3;  // ~(the smallest such chunk id) (atomic max), 0 = none
-constexpr int kFoldBadLen = 4;    // NEW chunks of length 0 or > chunk_size
-constexpr int kFoldBadLen1 = 5;   // ~(the smallest such chunk id), 0 = none
-constexpr int kFoldBadLayer1 = 6; // ~(the smallest layer whose bounds are out of order), 0 = none
-constexpr int kFoldCtrWords = 8;
+// dict_fold.hip (dict fold, dict.hip).  ctr: kFoldCtrWords u64
+// (dict_fold_plan.hpp), zeroed on s by the caller before launch_fold_keep_scan.
 // Launches 1-3: keep word + NEW count per 64 chunks of res[0, n) (a lane per
 // chunk; kinds and the NEW chunks' lengths are checked in the same pass), the
 // scan of the counts, then each layer's blob rank (the number of earlier layers
@@ -339,10 +332,6 @@ void launch_fold_scatter(const ngpu_result *res, const ngpu_chunk *chunks, uint6
                          const uint64_t *words, const uint32_t *prefix, const uint64_t *lfirst,
                          uint64_t L, const uint32_t *lrank, uint32_t blob0, uint32_t gid0,
                          DictRec *out, uint64_t k, hipStream_t s);
-// launch_dict_pack at an offset: blob0 added to every blob index, gid = gid0 + i.
-void launch_dict_pack_at(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,
-                         const uint32_t *index, const uint64_t *uoff, uint64_t n, uint32_t blob0,
-                         uint32_t gid0, DictRec *out, hipStream_t s);
 
 // node_fold.hip (node dict fold, node.hip).  The NEW chunks of res[0, n) per
 // owner part (owner_of over digest word 0, W <= 64) added to cnt[0, W), which the

@@ -511,14 +511,15 @@ __global__ void dict_unpack(const uint8_t *__restrict__ recs, uint64_t n,
 __global__ void dict_pack(const uint8_t *__restrict__ digests, const uint32_t *__restrict__ usize,
                           const uint32_t *__restrict__ blob, const uint32_t *__restrict__ index,
                           const uint64_t *__restrict__ uoff, const uint32_t *__restrict__ gid,
-                          uint64_t n, DictRec *__restrict__ out) {
+                          uint64_t n, uint32_t blob0, uint32_t gid0, DictRec *__restrict__ out) {
   const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint4 *dg = reinterpret_cast<const uint4 *>(digests + 32 * i);
   uint4 *o = reinterpret_cast<uint4 *>(out + i);
   o[0] = dg[0];
   o[1] = dg[1];
-  o[2] = make_uint4(usize[i], blob[i], index ? index[i] : 0, gid ? gid[i] : (uint32_t)i);
+  o[2] = make_uint4(usize[i], blob[i] + blob0, index ? index[i] : 0,
+                    gid ? gid[i] : gid0 + (uint32_t)i);
   const uint64_t u = uoff ? uoff[i] : 0;
   o[3] = make_uint4((uint32_t)u, (uint32_t)(u >> 32), 0, 0);
 }
@@ -1645,10 +1646,10 @@ void launch_dict_unpack(const uint8_t *recs, uint64_t n, const uint32_t *gids, u
 
 void launch_dict_pack(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,
                       const uint32_t *index, const uint64_t *uoff, const uint32_t *gid, uint64_t n,
-                      DictRec *out, hipStream_t s) {
+                      uint32_t blob0, uint32_t gid0, DictRec *out, hipStream_t s) {
   if (n == 0) return;
   hipLaunchKernelGGL(dict_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, digests, usize,
-                     blob, index, uoff, gid, n, out);
+                     blob, index, uoff, gid, n, blob0, gid0, out);
 }
 
 void launch_dedup(const ngpu_chunk *chunks, uint64_t n, const DictDevice &dict,

@@ -1,12 +1,9 @@
 // dict.hip — chunk dicts (PackOption.ChunkDictPath, builder.go:122-124) as
-// reference-counted HBM objects, and their C ABI (include/nydus_gpu.h).
-//
-// The reference hands `--chunk-dict bootstrap=P` to every nydus-image process
-// it spawns; each loads its own HashChunkDict ([nydus v2.3.0]
-// builder/src/core/chunk_dict.rs, external, VERIFY).  Here one load serves
-// every Pack that names the same unchanged file (the engine's open cache),
-// and a Pack pins the dict it was opened with, so packs against different
-// dicts can be open on one engine at once.
+// reference-counted HBM objects, and their C ABI (include/nydus_gpu.h): storage
+// and handles, create, extend, retire, fold, export and probe.  Loading one from
+// a bootstrap file, and the engine's open cache, are dict_load.hip.  A Pack pins
+// the dict it was opened with, so packs against different dicts can be open on
+// one engine at once.
 //
 // Layout in HBM per dict of m entries (table order): 64-B records (digest,
 // usize, blob, index, global id, uoff), hash slots u64[next_pow2(2m+16)] (open
@@ -17,18 +14,12 @@
 // handle on the same storage when there is room, else on a larger one; so do
 // ngpu_dict_fold and ngpu_dict_extend_device ("dict fold"), whose new records
 // are written by a kernel from tables that already lie in HBM.
-#include <errno.h>
-#include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <string>
-#include <thread>
 
 #include "blob.hpp"
 #include "dict_fold_plan.hpp"
@@ -38,8 +29,6 @@
 #include "host_window.hpp"
 
 using namespace ngpu;
-
-extern "C" const char *ngpu_host_error(void);
 
 namespace ngpu {
 
@@ -147,25 +136,183 @@ ngpu_dict *dict_new(ngpu_engine *e) {
   return d;
 }
 
-namespace {
+ngpu_dict *dict_derive(const ngpu_dict *base) {
+  ngpu_dict *d = new ngpu_dict();
+  d->device = base->device;
+  d->digester = base->digester;
+  d->chunk_size = base->chunk_size;
+  d->replicated = base->replicated;
+  d->routed = base->routed;
+  return d;
+}
 
 // A dict build runs on a stream of its own, outside the engine lock: a load
 // of a 200M-entry bootstrap takes seconds, and under e->mu (round 3) it stalled
 // every Pack of the engine for that long, while its stream syncs on the
 // engine's own stream waited for their work too.
-struct BuildStream {
-  hipStream_t s = nullptr;
-  explicit BuildStream(int device) {
-    DeviceGuard g(device);
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
-      (void)hipGetLastError();
-      s = nullptr;
-    }
+BuildStream::BuildStream(int device) {
+  DeviceGuard g(device);
+  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    s = nullptr;
   }
-  ~BuildStream() {
-    if (s) (void)hipStreamDestroy(s);
+}
+BuildStream::~BuildStream() {
+  if (s) (void)hipStreamDestroy(s);
+}
+
+void place_rows_from_records(const uint8_t *recs, uint64_t k, DictPlace *dst) {
+  for (uint64_t i = 0; i < k; ++i) {
+    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
+    dst[i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
+  }
+}
+
+int blob_count_verdict(ngpu_engine *e, uint64_t seen, uint32_t n_blobs, uint32_t *nb) {
+  if (n_blobs) {
+    if (seen > n_blobs)
+      return fail(e, NGPU_EFORMAT, "chunk dict record points at blob %u of %u", (uint32_t)(seen - 1),
+                  n_blobs);
+    seen = n_blobs;
+  }
+  if (seen > (1u << 20))
+    return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", (uint32_t)(seen - 1));
+  *nb = (uint32_t)seen;
+  return 0;
+}
+
+int records_blob_count(ngpu_engine *e, const uint8_t *recs, uint64_t k, uint32_t n_blobs,
+                       uint32_t *nb) {
+  uint64_t seen = 0;  // (64 bits: index 0xFFFFFFFF + 1 does not wrap to "no blob")
+  for (uint64_t i = 0; i < k; ++i) {
+    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
+    seen = std::max<uint64_t>(seen, (uint64_t)r->blob_index + 1);
+  }
+  return blob_count_verdict(e, seen, n_blobs, nb);
+}
+
+void dict_merge_blob_table(ngpu_dict *d, const ngpu_dict *base, bool with_table,
+                           const uint8_t *blobs, uint32_t n_blobs) {
+  if (!with_table) return;
+  d->blob_table = base->blob_table;
+  if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
+}
+
+int dict_plain_base_check(ngpu_engine *e, const ngpu_dict *base, const char *what,
+                          const char *node_hint) {
+  if (!base->parts.empty()) return fail(e, NGPU_EINVAL, "%s: %s", what, node_hint);
+  if (base->device != e->device)
+    return fail(e, NGPU_EINVAL, "chunk dict lives on device %d, engine on %d", base->device,
+                e->device);
+  return dict_check(e, base);
+}
+
+int grow_kept(ngpu_engine *e, uint8_t **ptr, uint64_t *cap, uint64_t bytes, const char *msg) {
+  if (bytes <= *cap) return 0;
+  // (nothing of an earlier fold still runs: each is complete when it returns)
+  if (*ptr) (void)hipFree(*ptr);
+  *ptr = nullptr;
+  *cap = 0;
+  const uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 1u << 16);
+  if (hipMalloc((void **)ptr, want) != hipSuccess) {
+    (void)hipGetLastError();
+    *ptr = nullptr;
+    return fail(e, NGPU_ENOMEM, "%s", msg);
+  }
+  *cap = want;
+  return 0;
+}
+
+int storage_alloc_place_only(ngpu_engine *e, uint64_t cap, DictStorage **out) {
+  DictStorage *st = new DictStorage();
+  st->device = e->device;
+  st->rec_cap = cap;
+  st->table_cap = ~0ull;
+  if (cap && !(st->place = (DictPlace *)malloc(cap * sizeof(DictPlace)))) {
+    delete st;
+    return fail(e, NGPU_ENOMEM, "chunk dict: no host memory for %llu placement rows",
+                (unsigned long long)cap);
+  }
+  *out = st;
+  return 0;
+}
+
+namespace {
+
+// NGPU_DICT_TRACE=1: one stderr line per extend, fold or retire with its device
+// time between HIP events (tools/dict_*_bench.py read them); off: no event is made.
+struct DictTrace {
+  hipEvent_t ev[4] = {};
+  bool on = false;
+  static bool enabled() {
+    static const bool t = [] {
+      const char *v = getenv("NGPU_DICT_TRACE");
+      return v && v[0] == '1';
+    }();
+    return t;
+  }
+  explicit DictTrace(int n, bool want = true) {
+    if (!want || !enabled()) return;
+    on = true;
+    for (int i = 0; i < n; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) ev[i] = nullptr, on = false;
+  }
+  ~DictTrace() {
+    for (hipEvent_t x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+  void record(int i, hipStream_t s) {
+    if (on) (void)hipEventRecord(ev[i], s);
+  }
+  // microseconds from event i to event j, both complete; < 0: not timed
+  double us(int i, int j) const {
+    float ms = 0;
+    return on && hipEventElapsedTime(&ms, ev[i], ev[j]) == hipSuccess ? ms * 1000.0 : -1.0;
   }
 };
+
+// dict_upload_unpack's staging buffers; hipFree waits for the device, so they outlive the caller's sync.
+struct DictStaging {
+  uint8_t *tmp = nullptr;
+  uint32_t *tmp_gid = nullptr;
+  int reserve(ngpu_engine *e, uint64_t k, bool with_gids) {
+    const uint64_t batch = std::min<uint64_t>(k, 1u << 20);
+    if (!k || tmp) return 0;
+    if (hipMalloc((void **)&tmp, batch * 80) != hipSuccess ||
+        (with_gids && hipMalloc((void **)&tmp_gid, batch * 4) != hipSuccess)) {
+      (void)hipGetLastError();
+      return fail(e, NGPU_ENOMEM, "chunk dict: staging allocation failed");
+    }
+    return 0;
+  }
+  ~DictStaging() {
+    if (tmp_gid) (void)hipFree(tmp_gid);
+    if (tmp) (void)hipFree(tmp);
+  }
+};
+
+// k host 80-B records into dst_rec[0, k) on s, in batches of <= 1M through stg: gid =
+// gids[i] (null: gid0 + i), blob0 added to every blob index.  Synced between batches, not
+// after the last (the caller's sync serves).  first(): after the first upload, before its launch.
+template <class First>
+int dict_upload_unpack(ngpu_engine *e, DictStaging &stg, const uint8_t *recs, const uint32_t *gids,
+                       uint64_t k, uint32_t gid0, uint32_t blob0, DictRec *dst_rec, hipStream_t s,
+                       First first) {
+  if (int rc = stg.reserve(e, k, gids != nullptr)) return rc;
+  const uint64_t batch = std::min<uint64_t>(k, 1u << 20);
+  for (uint64_t a = 0; a < k; a += batch) {
+    const uint64_t c = std::min(batch, k - a);
+    if (hipMemcpyAsync(stg.tmp, recs + 80 * a, c * 80, hipMemcpyHostToDevice, s) != hipSuccess ||
+        (gids && hipMemcpyAsync(stg.tmp_gid, gids + a, c * 4, hipMemcpyHostToDevice, s) != hipSuccess))
+      return fail(e, NGPU_EHIP, "chunk dict: upload failed");
+    if (a == 0) first();
+    launch_dict_unpack(stg.tmp, c, gids ? stg.tmp_gid : nullptr, gid0 + (uint32_t)a, dst_rec + a, s,
+                       blob0);
+    if (a + c < k && hipStreamSynchronize(s) != hipSuccess)
+      return fail(e, NGPU_EHIP, "chunk dict: unpack failed");
+  }
+  return 0;
+}
 
 }  // namespace
 
@@ -188,52 +335,17 @@ int dict_from_records(ngpu_engine *e, const uint8_t *recs, uint64_t m, const uin
   if (m >= 0xFFFFFFFFull) return fail(e, NGPU_EINVAL, "chunk dict too large (%llu entries)",
                                       (unsigned long long)m);
   uint32_t nb = 0;
-  for (uint64_t i = 0; i < m; ++i) {
-    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-    nb = std::max(nb, r->blob_index + 1);
-  }
-  if (n_blobs) {
-    if (nb > n_blobs)
-      return fail(e, NGPU_EFORMAT, "chunk dict record points at blob %u of %u", nb - 1, n_blobs);
-    nb = n_blobs;
-  }
-  if (nb > (1u << 20)) return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", nb - 1);
+  if (int rc = records_blob_count(e, recs, m, n_blobs, &nb)) return rc;
   ngpu_dict *d = dict_new(e);
   int rc = dict_alloc(e, d, m, nb, true);
   if (rc) {
     dict_unref(d);
     return rc;
   }
-  for (uint64_t i = 0; i < m; ++i) {
-    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-    d->st->place[i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
-  }
+  place_rows_from_records(recs, m, d->st->place);
   if (blobs && n_blobs) d->blob_table.assign(blobs, blobs + 256ull * n_blobs);
-  // upload in batches of <= 1M records, unpack to dict records on the GPU
-  const uint64_t batch = std::min<uint64_t>(m, 1u << 20);
-  uint8_t *tmp = nullptr;
-  uint32_t *tmp_gid = nullptr;
-  if (m && (hipMalloc((void **)&tmp, batch * 80) != hipSuccess ||
-            (gids && hipMalloc((void **)&tmp_gid, batch * 4) != hipSuccess))) {
-    if (tmp) (void)hipFree(tmp);
-    dict_unref(d);
-    return fail(e, NGPU_ENOMEM, "chunk dict: staging allocation failed");
-  }
-  DictRec *rec = const_cast<DictRec *>(d->dev.rec);
-  for (uint64_t a = 0; a < m && !rc; a += batch) {
-    const uint64_t k = std::min(batch, m - a);
-    if (hipMemcpyAsync(tmp, recs + 80 * a, k * 80, hipMemcpyHostToDevice, bs.s) != hipSuccess ||
-        (gids && hipMemcpyAsync(tmp_gid, gids + a, k * 4, hipMemcpyHostToDevice, bs.s) !=
-                     hipSuccess)) {
-      rc = fail(e, NGPU_EHIP, "chunk dict: upload failed");
-      break;
-    }
-    launch_dict_unpack(tmp, k, gids ? tmp_gid : nullptr, (uint32_t)a, rec + a, bs.s);
-    // the next batch overwrites tmp
-    if (hipStreamSynchronize(bs.s) != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: unpack failed");
-  }
-  if (tmp_gid) (void)hipFree(tmp_gid);
-  if (tmp) (void)hipFree(tmp);
+  DictStaging stg;
+  rc = dict_upload_unpack(e, stg, recs, gids, m, 0, 0, const_cast<DictRec *>(d->dev.rec), bs.s, [] {});
   if (!rc) rc = dict_build(e, d, bs.s);
   if (rc) {
     dict_unref(d);
@@ -278,7 +390,7 @@ int dict_from_arrays(ngpu_engine *e, const uint8_t *dg, const uint32_t *us, cons
         hipStreamSynchronize(bs.s) != hipSuccess)
       rc = fail(e, NGPU_EHIP, "chunk dict: upload failed");
   } else if (m) {
-    launch_dict_pack(dg, us, bl, ix, uo, gid, m, rec, bs.s);
+    launch_dict_pack(dg, us, bl, ix, uo, gid, m, 0, 0, rec, bs.s);
     if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: pack failed");
   }
   if (!rc) rc = dict_build(e, d, bs.s);
@@ -310,16 +422,7 @@ int dict_extend_check(ngpu_engine *e, const ngpu_dict *base, const uint8_t *recs
   if (m >= kDictMaxEntries || k >= kDictMaxEntries - m)
     return fail(e, NGPU_EINVAL, "chunk dict too large (%llu entries)", (unsigned long long)(m + k));
   uint32_t nb = 0;
-  for (uint64_t i = 0; i < k; ++i) {
-    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-    if (n_blobs && r->blob_index >= n_blobs)
-      return fail(e, NGPU_EFORMAT, "chunk dict record points at blob %u of %u", r->blob_index,
-                  n_blobs);
-    if (r->blob_index >= (1u << 20))
-      return fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", r->blob_index);
-    nb = std::max(nb, r->blob_index + 1);
-  }
-  if (n_blobs) nb = n_blobs;
+  if (int rc = records_blob_count(e, recs, k, n_blobs, &nb)) return rc;
   return dict_extend_check_blobs(e, base, k, nb, blobs && n_blobs, n_blobs, nb_out, with_table);
 }
 
@@ -391,65 +494,36 @@ int dict_extend_rows(ngpu_engine *e, ngpu_dict *base, const DictRowSource &src, 
     // a device source brings the stream its inputs are ordered on
     std::unique_ptr<BuildStream> own(src.stream ? nullptr : new BuildStream(e->device));
     const hipStream_t bs = src.stream ? src.stream : own->s;
-    const uint64_t batch = std::min<uint64_t>(k, 1u << 20);
-    uint8_t *tmp = nullptr;
-    uint32_t *tmp_gid = nullptr;
-    if (!bs) {
+    DictStaging stg;
+    if (!bs)
       rc = fail(e, NGPU_EHIP, "chunk dict: no build stream");
-    } else if (staged && (hipMalloc((void **)&tmp, batch * 80) != hipSuccess ||
-                          (gids && hipMalloc((void **)&tmp_gid, batch * 4) != hipSuccess))) {
-      (void)hipGetLastError();
-      rc = fail(e, NGPU_ENOMEM, "chunk dict: staging allocation failed");
-    }
-    // NGPU_DICT_TRACE=1: one stderr line per extend with its device time -- an
-    // in-place append from before its first launch (after the records' upload)
-    // to the end of the inserts, a copy from before the device-to-device copy to
-    // the end of the table build (tools/dict_extend_bench.py reads it); off: no
-    // event is made
-    static const bool trace = [] {
-      const char *v = getenv("NGPU_DICT_TRACE");
-      return v && v[0] == '1';
-    }();
-    hipEvent_t tev[2] = {};
-    if (!rc && trace)
-      for (hipEvent_t &x : tev)
-        if (hipEventCreate(&x) != hipSuccess) x = nullptr;
-    if (!share && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs);
+    else if (staged)
+      rc = stg.reserve(e, k, gids != nullptr);
+    // the trace line's device time: an in-place append from before its first
+    // launch (after the records' upload) to the end of the inserts, a copy from
+    // before the device-to-device copy to the end of the table build
+    DictTrace tr(2, !rc);
+    if (!share) tr.record(0, bs);
     if (!rc && !share && m &&
         hipMemcpyAsync(dst->rec, st->rec, m * sizeof(DictRec), hipMemcpyDeviceToDevice, bs) !=
             hipSuccess)
       rc = fail(e, NGPU_EHIP, "chunk dict: copy of the base's records failed");
     if (!rc && want_place) {
       if (!share && base->has_place) memcpy(dst->place, st->place, m * sizeof(DictPlace));
-      if (!staged) {
-        if (src.rows) memcpy(dst->place + m, src.rows, k * sizeof(DictPlace));
-      } else {
-        for (uint64_t i = 0; i < k; ++i) {
-          const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-          dst->place[m + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
-        }
-      }
+      if (staged)
+        place_rows_from_records(recs, k, dst->place + m);
+      else if (src.rows)
+        memcpy(dst->place + m, src.rows, k * sizeof(DictPlace));
     }
-    // launch 1 (per batch of <= 1M records): rec[m + a ..) from the 80-B records
-    for (uint64_t a = 0; staged && a < k && !rc; a += batch) {
-      const uint64_t c = std::min(batch, k - a);
-      if (hipMemcpyAsync(tmp, recs + 80 * a, c * 80, hipMemcpyHostToDevice, bs) != hipSuccess ||
-          (gids && hipMemcpyAsync(tmp_gid, gids + a, c * 4, hipMemcpyHostToDevice, bs) !=
-                       hipSuccess)) {
-        rc = fail(e, NGPU_EHIP, "chunk dict: upload failed");
-        break;
-      }
-      if (share && a == 0 && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs);
-      launch_dict_unpack(tmp, c, gids ? tmp_gid : nullptr, (uint32_t)(m + a), dst->rec + m + a, bs,
-                         src.blob0);
-      // the next batch overwrites tmp (one batch: the sync after the inserts serves)
-      if (a + c < k && hipStreamSynchronize(bs) != hipSuccess)
-        rc = fail(e, NGPU_EHIP, "chunk dict: unpack failed");
-    }
-    // (device source) launch 1: its own kernel writes rec[m, m + k)
-    if (!staged && !rc) {
-      if (share && tev[0] && tev[1]) (void)hipEventRecord(tev[0], bs);
-      src.write(src, dst->rec + m, m, bs);
+    // launch 1: rec[m, m + k) from the 80-B records (per batch of <= 1M; one
+    // batch: the sync after the inserts serves), or (device source) by its own kernel
+    if (staged && !rc) {
+      rc = dict_upload_unpack(e, stg, recs, gids, k, (uint32_t)m, src.blob0, dst->rec + m, bs, [&] {
+        if (share) tr.record(0, bs);
+      });
+    } else if (!rc) {
+      if (share) tr.record(0, bs);
+      src.write(dst->rec + m, m, bs);
       if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: record write failed");
     }
     // launch 2, after every record is written: the new ids into the live table
@@ -461,34 +535,23 @@ int dict_extend_rows(ngpu_engine *e, ngpu_dict *base, const DictRowSource &src, 
         launch_dict_build(dst->rec, m + k, dst->table, dst->table_cap, bs);
       if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: table insert failed");
     }
-    if (tev[0] && tev[1]) (void)hipEventRecord(tev[1], bs);
+    tr.record(1, bs);
     if (bs && hipStreamSynchronize(bs) != hipSuccess && !rc)
       rc = fail(e, NGPU_EHIP, "chunk dict: extend failed");
-    if (tev[0] && tev[1]) {
-      float ms = 0;
-      if (!rc && hipEventElapsedTime(&ms, tev[0], tev[1]) == hipSuccess) {
-        if (staged)
-          fprintf(stderr, "ngpu dict_extend %s m=%llu k=%llu device_us=%.1f\n", share ? "share" : "fork",
-                  (unsigned long long)m, (unsigned long long)k, ms * 1000.0);
-        else  // the fold's keep + scan ran before the counts came back
-          fprintf(stderr, "ngpu %s %s m=%llu k=%llu n=%llu device_us=%.1f keep_scan_us=%.1f\n", src.name,
-                  share ? "share" : "fork", (unsigned long long)m, (unsigned long long)k,
-                  (unsigned long long)src.n, ms * 1000.0 + src.pre_us, src.pre_us);
-      }
-    }
-    for (hipEvent_t x : tev)
-      if (x) (void)hipEventDestroy(x);
-    if (tmp_gid) (void)hipFree(tmp_gid);
-    if (tmp) (void)hipFree(tmp);
+    const double us = rc ? -1.0 : tr.us(0, 1);
+    if (us >= 0 && staged)
+      fprintf(stderr, "ngpu dict_extend %s m=%llu k=%llu device_us=%.1f\n", share ? "share" : "fork",
+              (unsigned long long)m, (unsigned long long)k, us);
+    else if (us >= 0)  // the fold's keep + scan ran before the counts came back
+      fprintf(stderr, "ngpu %s %s m=%llu k=%llu n=%llu device_us=%.1f keep_scan_us=%.1f\n", src.name,
+              share ? "share" : "fork", (unsigned long long)m, (unsigned long long)k,
+              (unsigned long long)src.n, us + src.pre_us, src.pre_us);
   }
   if (rc) {
     storage_unref(dst);
     return rc;
   }
-  ngpu_dict *d = new ngpu_dict();
-  d->device = base->device;
-  d->digester = base->digester;
-  d->chunk_size = base->chunk_size;
+  ngpu_dict *d = dict_derive(base);
   d->st = dst;
   d->has_place = want_place && m + k;
   d->shares_base = share;
@@ -517,23 +580,14 @@ static int place_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, co
   } else {
     // creation (no base): exactly k rows; a fork: half as many again
     const uint64_t cap = st ? dict_grow_plan(m, m + 1, 0, 0, k).rec_cap : k;
-    st = new DictStorage();
-    st->device = e->device;
-    st->rec_cap = cap;
-    st->table_cap = ~0ull;
+    if (int rc = storage_alloc_place_only(e, cap, &st)) return rc;
     st->used = m + k;
-    if (cap && !(st->place = (DictPlace *)malloc(cap * sizeof(DictPlace)))) {
-      delete st;
-      return fail(e, NGPU_ENOMEM, "chunk dict: no host memory for %llu placement rows",
-                  (unsigned long long)cap);
-    }
     if (base_rows) memcpy(st->place, base->st->place, m * sizeof(DictPlace));
   }
-  if (!recs && k) memcpy(st->place + m, rows, k * sizeof(DictPlace));
-  for (uint64_t i = 0; recs && i < k; ++i) {
-    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-    st->place[m + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
-  }
+  if (recs)
+    place_rows_from_records(recs, k, st->place + m);
+  else if (k)
+    memcpy(st->place + m, rows, k * sizeof(DictPlace));
   out->st = st;
   out->has_place = m + k != 0;
   return 0;
@@ -593,29 +647,18 @@ int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector
   const uint64_t nw = (m + 63) / 64, nt = dict_retire_scan_tiles(m);
   BuildStream bs(e->device);
   if (!bs.s) return fail(e, NGPU_EHIP, "chunk dict: no build stream");
-  // one scratch allocation: keep words, tile sums (+ the total), word counts /
-  // prefixes, the retire bitmap and the blob remap
-  const uint64_t o_sums = 8 * nw, o_cnt = o_sums + 8 * (nt + 1), o_bits = o_cnt + 4 * nw,
-                 o_remap = o_bits + 4 * bitmap.size(), bytes = o_remap + 4 * remap.size();
+  const RetireScratch lay = retire_scratch_layout(m, bitmap.size(), remap.size());
   uint8_t *scr = nullptr;
-  if (hipMalloc((void **)&scr, bytes) != hipSuccess) {
+  if (hipMalloc((void **)&scr, lay.bytes) != hipSuccess) {
     (void)hipGetLastError();
     return fail(e, NGPU_ENOMEM, "dict retire: scratch allocation failed");
   }
-  uint64_t *d_words = (uint64_t *)scr, *d_sums = (uint64_t *)(scr + o_sums);
-  uint32_t *d_cnt = (uint32_t *)(scr + o_cnt), *d_bits = (uint32_t *)(scr + o_bits),
-           *d_remap = (uint32_t *)(scr + o_remap);
-  // NGPU_DICT_TRACE=1: one stderr line per retire with its device time, launches
-  // 1-2 plus launches 3-4 (the allocation between them is host time)
-  static const bool trace = [] {
-    const char *v = getenv("NGPU_DICT_TRACE");
-    return v && v[0] == '1';
-  }();
-  hipEvent_t tev[4] = {};
-  bool timed = trace;
-  if (trace)
-    for (hipEvent_t &x : tev)
-      if (hipEventCreate(&x) != hipSuccess) x = nullptr, timed = false;
+  uint64_t *d_words = (uint64_t *)(scr + lay.words), *d_sums = (uint64_t *)(scr + lay.sums);
+  uint32_t *d_cnt = (uint32_t *)(scr + lay.cnt), *d_bits = (uint32_t *)(scr + lay.bits),
+           *d_remap = (uint32_t *)(scr + lay.remap);
+  // the trace line's device time: launches 1-2 plus launches 3-4 (the allocation
+  // between them is host time)
+  DictTrace tr(4);
   int rc = 0;
   DictStorage *dst = nullptr;
   DictKeep own_keep;
@@ -626,11 +669,11 @@ int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector
                                         hipMemcpyHostToDevice, bs.s) != hipSuccess))
     rc = fail(e, NGPU_EHIP, "dict retire: upload failed");
   if (!rc) {
-    if (timed) (void)hipEventRecord(tev[0], bs.s);
+    tr.record(0, bs.s);
     launch_dict_keep_scan(base->st ? base->st->rec : nullptr, m, d_bits, nb0, d_words, d_cnt, d_sums,
                           bs.s);
     if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict retire: keep scan failed");
-    if (timed) (void)hipEventRecord(tev[1], bs.s);
+    tr.record(1, bs.s);
   }
   if (!rc && (place || keep) && nw) {
     hk.words.resize(nw);
@@ -648,35 +691,27 @@ int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector
     rc = storage_alloc(e, dict_retire_rec_cap(s), dict_retire_table_cap(s), place && s, &dst);
   if (!rc) {
     dst->used = s;
-    if (timed) (void)hipEventRecord(tev[2], bs.s);
+    tr.record(2, bs.s);
     launch_dict_compact(base->st ? base->st->rec : nullptr, m, d_words, d_cnt, d_remap, nb0, dst->rec,
                         s, bs.s);
     launch_dict_build(dst->rec, s, dst->table, dst->table_cap, bs.s);
     if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict retire: compaction failed");
-    if (timed) (void)hipEventRecord(tev[3], bs.s);
+    tr.record(3, bs.s);
   }
   // the placement rows, while the device moves the records
   if (!rc && place && s) dict_retire_place(hk, m, place, dst->place, s);
   if (hipStreamSynchronize(bs.s) != hipSuccess && !rc)
     rc = fail(e, NGPU_EHIP, "dict retire: compaction failed");
-  if (timed) {
-    float a = 0, b = 0;
-    if (!rc && hipEventElapsedTime(&a, tev[0], tev[1]) == hipSuccess &&
-        hipEventElapsedTime(&b, tev[2], tev[3]) == hipSuccess)
-      fprintf(stderr, "ngpu dict_retire m=%llu s=%llu device_us=%.1f keep_scan_us=%.1f compact_build_us=%.1f\n",
-              (unsigned long long)m, (unsigned long long)s, (a + b) * 1000.0, a * 1000.0, b * 1000.0);
-  }
-  for (hipEvent_t x : tev)
-    if (x) (void)hipEventDestroy(x);
+  const double a = rc ? -1.0 : tr.us(0, 1), b = rc ? -1.0 : tr.us(2, 3);
+  if (a >= 0 && b >= 0)
+    fprintf(stderr, "ngpu dict_retire m=%llu s=%llu device_us=%.1f keep_scan_us=%.1f compact_build_us=%.1f\n",
+            (unsigned long long)m, (unsigned long long)s, a + b, a, b);
   (void)hipFree(scr);
   if (rc) {
     storage_unref(dst);
     return rc;
   }
-  ngpu_dict *d = new ngpu_dict();
-  d->device = base->device;
-  d->digester = base->digester;
-  d->chunk_size = base->chunk_size;
+  ngpu_dict *d = dict_derive(base);
   d->st = dst;
   d->has_place = place && s;
   dict_bind(d, s, nb);
@@ -723,341 +758,9 @@ static int dict_export_records(ngpu_engine *e, const ngpu_dict *p, const DictPla
   return 0;
 }
 
-namespace {
-
-// RafsSuperFlags HASH_SHA256 (0x8) -> sha256, else blake3 ([nydus v2.3.0]
-// RafsSuperMeta::get_digester, VERIFY; the fixture's ext flags are 0x6).
-uint32_t digester_of_flags(uint64_t f) { return (f & 0x8) ? NGPU_DIGEST_SHA256 : NGPU_DIGEST_BLAKE3; }
-
-int read_at(FILE *f, void *buf, uint64_t n, uint64_t off) {
-  if (!n) return 0;
-  if (fseeko(f, (off_t)off, SEEK_SET) != 0 || fread(buf, 1, n, f) != n) return -1;
-  return 0;
-}
-
-}  // namespace
-
-namespace {
-
-// A RAFS v5 chunk-dict bootstrap (FsVersion "5" with ChunkDictPath): parsed
-// by the host code (parse_v5_bootstrap, blob.cpp), checked against the engine.
-int parse_v5_dict(ngpu_engine *e, const char *path, const std::vector<uint8_t> &b,
-                  std::vector<uint8_t> *recs_out, std::vector<uint8_t> *blobs_out) {
-  uint32_t dg = 0, bs = 0;
-  if (int rc = parse_v5_bootstrap(b.data(), b.size(), &dg, &bs, recs_out, blobs_out))
-    return fail(e, rc, "chunk dict %s: %s", path, ngpu_host_error());
-  if (dg != e->cfg.digester)
-    return fail(e, NGPU_EINVAL, "chunk dict %s: inconsistent digester %s vs %s", path,
-                dg ? "sha256" : "blake3", e->cfg.digester ? "sha256" : "blake3");
-  if (bs != e->cfg.chunk_size)
-    return fail(e, NGPU_EINVAL, "chunk dict %s: inconsistent chunk size 0x%x vs 0x%x", path, bs,
-                e->cfg.chunk_size);
-  return 0;
-}
-
-}  // namespace
-
-// Parse + check a chunk-dict bootstrap against engine e's options: its chunk
-// records (80 B each) and blob table (256 B each).  RAFS v6 for a FsVersion
-// 6 engine, RAFS v5 for FsVersion 5; the other pairings are nydus-image's
-// "inconsistent RAFS version" error.
-int read_dict_bootstrap(ngpu_engine *e, const char *path, uint64_t file_size,
-                        std::vector<uint8_t> *recs_out, std::vector<uint8_t> *blobs_out,
-                        uint64_t *table_at) {
-  FILE *f = fopen(path, "rb");
-  if (!f) return fail(e, NGPU_EIO, "open chunk dict %s", path);
-  uint8_t sb[kRafsV6ExtSuperBlockOffset + 256];
-  uint32_t magic = 0, magic5 = 0, ver5 = 0;
-  const bool got_sb = file_size >= sizeof sb && read_at(f, sb, sizeof sb, 0) == 0;
-  if (got_sb) {
-    memcpy(&magic, sb + kRafsV6SuperBlockOffset, 4);
-    memcpy(&magic5, sb, 4);
-    memcpy(&ver5, sb + 4, 4);
-  }
-  const bool v6 = got_sb && magic == kRafsV6Magic;
-  const bool v5 = got_sb && magic5 == kRafsV5Magic && ver5 == kRafsV5Version;
-  if (!v5 && !v6) {
-    fclose(f);
-    return fail(e, NGPU_EFORMAT, "chunk dict %s is not a RAFS v5/v6 bootstrap", path);
-  }
-  if ((v6 ? 6u : 5u) != e->cfg.fs_version) {
-    fclose(f);
-    return fail(e, NGPU_EINVAL,
-                "chunk dict %s: RAFS v%d bootstrap for a FsVersion %u engine (inconsistent version)",
-                path, v6 ? 6 : 5, e->cfg.fs_version);
-  }
-  if (v5) {
-    std::vector<uint8_t> all(file_size);
-    const int r = read_at(f, all.data(), file_size, 0);
-    fclose(f);
-    if (r) return fail(e, NGPU_EIO, "chunk dict %s: short read", path);
-    return parse_v5_dict(e, path, all, recs_out, blobs_out);
-  }
-  const uint8_t *x = sb + kRafsV6ExtSuperBlockOffset;
-  uint64_t flags, bto, cto, cts;
-  uint32_t bts, cs;
-  memcpy(&flags, x, 8);
-  memcpy(&bto, x + 8, 8);
-  memcpy(&bts, x + 16, 4);
-  memcpy(&cs, x + 20, 4);
-  memcpy(&cto, x + 24, 8);  // RafsV6ChunkInfoOffset = 1024+128+24 (layout.go:27)
-  memcpy(&cts, x + 32, 8);
-  const uint32_t dg = digester_of_flags(flags);
-  int rc = 0;
-  if (dg != e->cfg.digester)
-    rc = fail(e, NGPU_EINVAL, "chunk dict %s: inconsistent digester %s vs %s", path,
-              dg ? "sha256" : "blake3", e->cfg.digester ? "sha256" : "blake3");
-  else if (cs != e->cfg.chunk_size)
-    rc = fail(e, NGPU_EINVAL, "chunk dict %s: inconsistent chunk size 0x%x vs 0x%x", path, cs,
-              e->cfg.chunk_size);
-  else if (cts % 80 || bts % 256 || cto > file_size || cts > file_size - cto || bto > file_size ||
-           bts > file_size - bto)
-    rc = fail(e, NGPU_EFORMAT, "chunk dict %s: bad chunk/blob table bounds", path);
-  if (!rc && table_at) {  // v6, records left in the file: the caller streams them
-    table_at[0] = cto;
-    table_at[1] = cts;
-    recs_out->clear();
-    blobs_out->resize(bts);
-    if (read_at(f, blobs_out->data(), bts, bto) != 0)
-      rc = fail(e, NGPU_EIO, "chunk dict %s: short read", path);
-  } else if (!rc) {
-    recs_out->resize(cts);
-    blobs_out->resize(bts);
-    if (read_at(f, recs_out->data(), cts, cto) != 0 || read_at(f, blobs_out->data(), bts, bto) != 0)
-      rc = fail(e, NGPU_EIO, "chunk dict %s: short read", path);
-  }
-  fclose(f);
-  return rc;
-}
-
-namespace {
-
-// A RAFS v6 chunk table streamed from the file into HBM:
-// 1M-record pieces (80 MB) go through three pinned buffers; kReadThreads host
-// threads pread a piece (page cache or disk) and scan it (blob index bound,
-// the compressed placements the blob writer keeps on the host) while the
-// previous pieces cross PCIe and the unpack kernel turns them into dict
-// records, so the file read, the H2D copy and the unpack overlap instead of
-// following one another over the whole table.  Same records, same table
-// order, same checks as dict_from_records.
-constexpr uint64_t kStreamPiece = 1u << 20;      // records per piece
-constexpr uint64_t kStreamMinBytes = 256u << 20;  // smaller tables: one read, dict_from_records
-constexpr int kReadThreads = 8;
-
-int pread_full(int fd, uint8_t *dst, uint64_t n, uint64_t off) {
-  while (n) {
-    const ssize_t r = pread(fd, dst, n, (off_t)off);
-    if (r <= 0) {
-      if (r < 0 && errno == EINTR) continue;
-      return -1;
-    }
-    dst += r, n -= (uint64_t)r, off += (uint64_t)r;
-  }
-  return 0;
-}
-
-int dict_stream_v6(ngpu_engine *e, const char *path, uint64_t cto, uint64_t m,
-                   const std::vector<uint8_t> &blobs, ngpu_dict **out) {
-  DeviceGuard dg(e->device);
-  BuildStream bs(e->device);
-  if (!bs.s) return fail(e, NGPU_EHIP, "chunk dict: no build stream");
-  if (m >= 0xFFFFFFFFull)
-    return fail(e, NGPU_EINVAL, "chunk dict too large (%llu entries)", (unsigned long long)m);
-  const uint32_t n_blobs = (uint32_t)(blobs.size() / 256);
-  const int fd = open(path, O_RDONLY | O_CLOEXEC);
-  if (fd < 0) return fail(e, NGPU_EIO, "open chunk dict %s", path);
-  ngpu_dict *d = dict_new(e);
-  uint8_t *pin[3] = {}, *tmp[2] = {};
-  hipEvent_t ev[3] = {};
-  int rc = dict_alloc(e, d, m, n_blobs, true);
-  for (int i = 0; i < 3 && !rc; ++i)
-    if (hipHostMalloc((void **)&pin[i], kStreamPiece * 80, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess)
-      rc = fail(e, NGPU_ENOMEM, "chunk dict: pinned staging allocation failed");
-  for (int i = 0; i < 2 && !rc; ++i)
-    if (hipMalloc((void **)&tmp[i], kStreamPiece * 80) != hipSuccess)
-      rc = fail(e, NGPU_ENOMEM, "chunk dict: staging allocation failed");
-  if (!rc && n_blobs) d->blob_table.assign(blobs.begin(), blobs.end());
-  DictRec *rec = const_cast<DictRec *>(d->dev.rec);
-  uint32_t nb = 0;
-  for (uint64_t a = 0, k = 0; a < m && !rc; a += kStreamPiece, ++k) {
-    const uint64_t cnt = std::min(kStreamPiece, m - a);
-    uint8_t *h = pin[k % 3];
-    if (k >= 3 && hipEventSynchronize(ev[k % 3]) != hipSuccess) {  // its last copy is done
-      rc = fail(e, NGPU_EHIP, "chunk dict: upload failed");
-      break;
-    }
-    // read + scan the piece on kReadThreads threads (disjoint record ranges)
-    std::atomic<int> bad{0};
-    uint32_t tnb[kReadThreads] = {};
-    std::vector<std::thread> th;
-    const uint64_t per = (cnt + kReadThreads - 1) / kReadThreads;
-    for (int t = 0; t < kReadThreads; ++t) {
-      const uint64_t r0 = std::min(cnt, per * t), r1 = std::min(cnt, per * (t + 1));
-      if (r0 == r1) continue;
-      th.emplace_back([&, r0, r1, t] {
-        if (pread_full(fd, h + 80 * r0, 80 * (r1 - r0), cto + 80 * (a + r0))) {
-          bad = 1;
-          return;
-        }
-        uint32_t x = 0;
-        for (uint64_t i = r0; i < r1; ++i) {
-          const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(h + 80 * i);
-          x = std::max(x, r->blob_index + 1);
-          d->st->place[a + i] = DictPlace{r->compressed_offset, r->compressed_size, r->flags};
-        }
-        tnb[t] = x;
-      });
-    }
-    for (auto &x : th) x.join();
-    for (uint32_t x : tnb) nb = std::max(nb, x);
-    if (bad) {
-      rc = fail(e, NGPU_EIO, "chunk dict %s: short read", path);
-      break;
-    }
-    if (hipMemcpyAsync(tmp[k % 2], h, cnt * 80, hipMemcpyHostToDevice, bs.s) != hipSuccess) {
-      rc = fail(e, NGPU_EHIP, "chunk dict: upload failed");
-      break;
-    }
-    launch_dict_unpack(tmp[k % 2], cnt, nullptr, (uint32_t)a, rec + a, bs.s);
-    if (hipEventRecord(ev[k % 3], bs.s) != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: unpack failed");
-  }
-  close(fd);
-  if (!rc && hipStreamSynchronize(bs.s) != hipSuccess) rc = fail(e, NGPU_EHIP, "chunk dict: unpack failed");
-  if (rc) (void)hipStreamSynchronize(bs.s);
-  for (uint8_t *x : tmp)
-    if (x) (void)hipFree(x);
-  for (int i = 0; i < 3; ++i) {
-    if (pin[i]) (void)hipHostFree(pin[i]);
-    if (ev[i]) (void)hipEventDestroy(ev[i]);
-  }
-  if (!rc && n_blobs && nb > n_blobs)
-    rc = fail(e, NGPU_EFORMAT, "chunk dict record points at blob %u of %u", nb - 1, n_blobs);
-  if (!rc && nb > (1u << 20)) rc = fail(e, NGPU_EINVAL, "chunk dict blob index %u too large", nb - 1);
-  if (!rc && !n_blobs) d->dev.n_blobs = nb;
-  if (!rc) rc = dict_build(e, d, bs.s);
-  if (rc) {
-    dict_unref(d);
-    return rc;
-  }
-  *out = d;
-  return 0;
-}
-
-// Parse + check + load a RAFS v5/v6 chunk-dict bootstrap (no engine lock).
-int dict_load_file(ngpu_engine *e, const char *path, const struct stat &st, ngpu_dict **out) {
-  std::vector<uint8_t> recs, blobs;
-  uint64_t table[2] = {0, 0};
-  int rc = read_dict_bootstrap(e, path, (uint64_t)st.st_size, &recs, &blobs, table);
-  if (rc) return rc;
-  ngpu_dict *d = nullptr;
-  if (table[1] >= kStreamMinBytes) {  // v6 and large: stream it
-    if ((rc = dict_stream_v6(e, path, table[0], table[1] / 80, blobs, &d))) return rc;
-  } else {
-    if (table[1]) {  // v6, small: one read
-      recs.resize(table[1]);
-      FILE *f = fopen(path, "rb");
-      rc = (!f || read_at(f, recs.data(), table[1], table[0]))
-               ? fail(e, NGPU_EIO, "chunk dict %s: short read", path)
-               : 0;
-      if (f) fclose(f);
-      if (rc) return rc;
-    }
-    if ((rc = dict_from_records(e, recs.data(), recs.size() / 80, blobs.data(), blobs.size() / 256,
-                                &d, nullptr)))
-      return rc;
-  }
-  d->path = path;
-  d->st_dev = st.st_dev;
-  d->st_ino = st.st_ino;
-  d->st_size = st.st_size;
-  d->st_mtime_ns = (int64_t)st.st_mtim.tv_sec * 1000000000 + st.st_mtim.tv_nsec;
-  *out = d;
-  return 0;
-}
-
-constexpr size_t kDictCache = 4;
-
-}  // namespace
 }  // namespace ngpu
 
 extern "C" {
-
-static int dict_open(ngpu_engine *e, const char *path, ngpu_dict **out);
-
-int ngpu_dict_open(ngpu_engine *e, const char *path, ngpu_dict **out) {
-  return guarded([&] { return dict_open(e, path, out); });
-}
-
-static bool same_file(const ngpu_dict *d, const char *path, const struct stat &st, int64_t mt) {
-  return d->path == path && d->st_dev == (uint64_t)st.st_dev && d->st_ino == (uint64_t)st.st_ino &&
-         d->st_size == (uint64_t)st.st_size && d->st_mtime_ns == mt;
-}
-
-// The engine lock covers only the cache lookups and the insert: the bootstrap
-// is read, parsed and built in HBM without it, and dicts leaving the cache are
-// released after it is dropped (the last release hipFrees, a device-wide wait).
-// Two threads opening the same changed file may both load it; the second
-// insert finds the first and drops its own copy.
-static int dict_open(ngpu_engine *e, const char *path, ngpu_dict **out) {
-  if (!e || !path || !out) return NGPU_EINVAL;
-  *out = nullptr;
-  struct stat st;
-  if (stat(path, &st) != 0) return fail(e, NGPU_EIO, "stat chunk dict %s", path);
-  const int64_t mt = (int64_t)st.st_mtim.tv_sec * 1000000000 + st.st_mtim.tv_nsec;
-  std::vector<ngpu_dict *> drop;
-  auto release_dropped = [&] {
-    for (ngpu_dict *x : drop) dict_unref(x);
-    drop.clear();
-  };
-  {
-    std::lock_guard<std::mutex> g(e->mu);
-    auto &c = e->dict_cache;
-    for (size_t i = 0; i < c.size(); ++i) {
-      ngpu_dict *d = c[i];
-      if (d->path != path) continue;
-      if (same_file(d, path, st, mt)) {
-        dict_ref(d);
-        *out = d;
-        return 0;
-      }
-      c.erase(c.begin() + (long)i);  // the file changed: forget the old load
-      drop.push_back(d);
-      break;
-    }
-  }
-  release_dropped();
-  ngpu_dict *d = nullptr;
-  if (int rc = dict_load_file(e, path, st, &d)) return rc;
-  {
-    std::lock_guard<std::mutex> g(e->mu);
-    auto &c = e->dict_cache;
-    for (ngpu_dict *x : c)
-      if (same_file(x, path, st, mt)) {  // another thread loaded it meanwhile
-        dict_ref(x);
-        drop.push_back(d);
-        d = x;
-        break;
-      }
-    if (std::find(c.begin(), c.end(), d) == c.end()) {
-      for (size_t i = 0; i < c.size(); ++i)
-        if (c[i]->path == path) {  // an older load of the same path
-          drop.push_back(c[i]);
-          c.erase(c.begin() + (long)i);
-          break;
-        }
-      if (c.size() >= kDictCache) {
-        drop.push_back(c.front());
-        c.erase(c.begin());
-      }
-      dict_ref(d);  // the cache's reference
-      c.push_back(d);
-    }
-  }
-  release_dropped();
-  *out = d;
-  return 0;
-}
 
 int ngpu_dict_create(ngpu_engine *e, const void *records, uint64_t n, const void *blob_table,
                      uint32_t n_blobs, ngpu_dict **out) {
@@ -1069,27 +772,25 @@ int ngpu_dict_create(ngpu_engine *e, const void *records, uint64_t n, const void
   });
 }
 
-static int dict_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t n,
-                       const uint8_t *blobs, uint32_t n_blobs, ngpu_dict **out) {
-  if (!base->parts.empty())
-    return fail(e, NGPU_EINVAL, "dict extend: a node dict is extended with ngpu_node_dict_extend");
-  if (base->device != e->device)
-    return fail(e, NGPU_EINVAL, "chunk dict lives on device %d, engine on %d", base->device,
-                e->device);
-  if (int rc = dict_check(e, base)) return rc;
+}  // extern "C"
+
+int ngpu::dict_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t n,
+                      const uint8_t *blobs, uint32_t n_blobs, ngpu_dict **out) {
+  if (int rc = dict_plain_base_check(e, base, "dict extend",
+                                     "a node dict is extended with ngpu_node_dict_extend"))
+    return rc;
   uint32_t nb = 0;
   bool with_table = false;
   if (int rc = dict_extend_check(e, base, recs, n, blobs, n_blobs, &nb, &with_table)) return rc;
   ngpu_dict *d = nullptr;
   if (int rc = dict_extend_records(e, base, recs, n, base->dev.n_blobs, nb, nullptr, true, &d))
     return rc;
-  if (with_table) {
-    d->blob_table = base->blob_table;
-    if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
-  }
+  dict_merge_blob_table(d, base, with_table, blobs, n_blobs);
   *out = d;
   return 0;
 }
+
+extern "C" {
 
 int ngpu_dict_extend(ngpu_engine *e, ngpu_dict *base, const void *records, uint64_t n,
                      const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out) {
@@ -1099,23 +800,6 @@ int ngpu_dict_extend(ngpu_engine *e, ngpu_dict *base, const void *records, uint6
   return guarded([&] {
     return dict_extend(e, base, (const uint8_t *)records, n, (const uint8_t *)blob_table, n_blobs,
                        out);
-  });
-}
-
-int ngpu_dict_extend_bootstrap(ngpu_engine *e, ngpu_dict *base, const char *path, uint32_t flags,
-                               ngpu_dict **out) {
-  if (out) *out = nullptr;
-  if (!base || flags || !e || !out || !path) return NGPU_EINVAL;
-  return guarded([&]() -> int {
-    if (e->cfg.fs_version != 6)
-      return fail(e, NGPU_EINVAL, "dict extend takes RAFS v6 bootstraps (FsVersion %u engine)",
-                  e->cfg.fs_version);
-    struct stat st;
-    if (stat(path, &st) != 0) return fail(e, NGPU_EIO, "stat chunk dict %s", path);
-    std::vector<uint8_t> recs, blobs;
-    if (int rc = read_dict_bootstrap(e, path, (uint64_t)st.st_size, &recs, &blobs)) return rc;
-    return dict_extend(e, base, recs.data(), recs.size() / 80, blobs.data(),
-                       (uint32_t)(blobs.size() / 256), out);
   });
 }
 
@@ -1145,68 +829,54 @@ int ngpu::fold_lane(ngpu_engine *e, uint64_t bytes) {
     e->fold_stream = nullptr;
     return fail(e, NGPU_EHIP, "chunk dict: no build stream");
   }
-  if (bytes > e->fold_scr_cap) {
-    // (nothing of an earlier fold still runs: each is complete when it returns)
-    if (e->fold_scr) (void)hipFree(e->fold_scr);
-    e->fold_scr = nullptr;
-    e->fold_scr_cap = 0;
-    const uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 1u << 16);
-    if (hipMalloc((void **)&e->fold_scr, want) != hipSuccess) {
-      (void)hipGetLastError();
-      e->fold_scr = nullptr;
-      return fail(e, NGPU_ENOMEM, "dict fold: scratch allocation failed");
-    }
-    e->fold_scr_cap = want;
+  return grow_kept(e, &e->fold_scr, &e->fold_scr_cap, bytes, "dict fold: scratch allocation failed");
+}
+
+int ngpu::fold_fail(ngpu_engine *e, const char *prefix, const FoldVerdict &v, uint64_t n, uint64_t L) {
+  switch (v.why) {
+    case FoldVerdict::ok: return 0;
+    case FoldVerdict::bad_layer:
+      return fail(e, NGPU_EINVAL,
+                  "%slayer_first is not 0 = first[0] <= ... <= first[%llu] = %llu at layer %llu", prefix,
+                  (unsigned long long)L, (unsigned long long)n, (unsigned long long)v.which);
+    case FoldVerdict::bad_kind:
+      return fail(e, NGPU_EINVAL,
+                  "%schunk %llu is no dedup result (its kind is none of NEW / INTRA / DICT; "
+                  "%llu such chunks)",
+                  prefix, (unsigned long long)v.which, (unsigned long long)v.count);
+    case FoldVerdict::bad_len:
+      return fail(e, NGPU_EINVAL,
+                  "%sNEW chunk %llu has length 0 or more than chunk size 0x%x (%llu such chunks)", prefix,
+                  (unsigned long long)v.which, e->cfg.chunk_size, (unsigned long long)v.count);
+    case FoldVerdict::insane: break;
   }
+  return fail(e, NGPU_EHIP, "%s%llu NEW chunks in %llu layers of %llu chunks", prefix,
+              (unsigned long long)v.k, (unsigned long long)v.b, (unsigned long long)n);
+}
+
+int ngpu::fold_place_fail(ngpu_engine *e, const char *prefix, DictFoldPlace pr, uint64_t n_placements,
+                          uint64_t k, bool rows_ok, uint32_t n_blobs, uint64_t b) {
+  if (pr == kPlaceCount)
+    return fail(e, NGPU_EINVAL, "%s%llu placements for %llu NEW chunks", prefix,
+                (unsigned long long)n_placements, (unsigned long long)k);
+  if (pr == kPlaceMissing)
+    return fail(e, NGPU_EINVAL, "%sthe base keeps compressed placements, the call gives none", prefix);
+  if (pr == kPlaceUnwanted)
+    return fail(e, NGPU_EINVAL, "%sthe base keeps no compressed placements, the call gives some",
+                prefix);
+  if (!rows_ok)
+    return fail(e, NGPU_EINVAL, "%sa blob table of %u rows for %llu layers with a NEW chunk", prefix,
+                n_blobs, (unsigned long long)b);
   return 0;
 }
 
-extern "C" {
-
-namespace {
-struct FoldArgs {
-  const ngpu_result *res;
-  const ngpu_chunk *chunks;
-  uint64_t n;
-  const uint64_t *words;
-  const uint32_t *prefix;
-  const uint64_t *lfirst;
-  uint64_t L;
-  const uint32_t *lrank;
-  uint32_t blob0;
-  uint64_t k;
-};
-void fold_write(const DictRowSource &src, DictRec *dst, uint64_t m, hipStream_t s) {
-  const FoldArgs &a = *static_cast<const FoldArgs *>(src.arg);
-  launch_fold_scatter(a.res, a.chunks, a.n, a.words, a.prefix, a.lfirst, a.L, a.lrank, a.blob0,
-                      (uint32_t)m, dst, a.k, s);
-}
-struct PackArgs {
-  const uint8_t *dg;
-  const uint32_t *us, *bl, *ix;
-  const uint64_t *uo;
-  uint64_t n;
-  uint32_t blob0;
-};
-void pack_write(const DictRowSource &src, DictRec *dst, uint64_t m, hipStream_t s) {
-  const PackArgs &a = *static_cast<const PackArgs *>(src.arg);
-  launch_dict_pack_at(a.dg, a.us, a.bl, a.ix, a.uo, a.n, a.blob0, (uint32_t)m, dst, s);
-}
-}  // namespace
-
-static int dict_fold_base_check(ngpu_engine *e, const ngpu_dict *base, const char *what) {
-  if (!base->parts.empty()) return fail(e, NGPU_EINVAL, "%s: node dicts are not supported", what);
-  if (base->device != e->device)
-    return fail(e, NGPU_EINVAL, "chunk dict lives on device %d, engine on %d", base->device,
-                e->device);
-  return dict_check(e, base);
-}
-
-static int dict_extend_device(ngpu_engine *e, ngpu_dict *base, const PackArgs &a, uint32_t n_blobs,
-                              ngpu_dict **out) {
-  if (int rc = dict_fold_base_check(e, base, "dict extend_device")) return rc;
+static int dict_extend_device(ngpu_engine *e, ngpu_dict *base, const uint8_t *dg, const uint32_t *us,
+                              const uint32_t *bl, const uint32_t *ix, const uint64_t *uo, uint64_t n,
+                              uint32_t n_blobs, ngpu_dict **out) {
+  if (int rc = dict_plain_base_check(e, base, "dict extend_device", "node dicts are not supported"))
+    return rc;
   ngpu_dict *d = nullptr;
-  if (a.n == 0) {  // a handle equal to base
+  if (n == 0) {  // a handle equal to base
     if (int rc = dict_extend_rows(e, base, DictRowSource{}, 0, base->dev.n_blobs, base->has_place, &d))
       return rc;
     d->blob_table = base->blob_table;
@@ -1215,26 +885,104 @@ static int dict_extend_device(ngpu_engine *e, ngpu_dict *base, const PackArgs &a
   }
   uint32_t nb = 0;
   bool with_table = false;
-  if (int rc = dict_extend_check_blobs(e, base, a.n, n_blobs, false, n_blobs, &nb, &with_table))
+  if (int rc = dict_extend_check_blobs(e, base, n, n_blobs, false, n_blobs, &nb, &with_table))
     return rc;
   if (base->has_place)
     return fail(e, NGPU_EINVAL,
                 "dict extend_device: the base keeps compressed placements, device arrays carry none");
   std::lock_guard<std::mutex> lane(e->fold_mu);
-  DeviceGuard dg(e->device);
+  DeviceGuard dgd(e->device);
   if (int rc = fold_lane(e, 0)) return rc;
-  PackArgs args = a;
-  args.blob0 = base->dev.n_blobs;
+  const uint32_t blob0 = base->dev.n_blobs;
+  auto write = [&](DictRec *dst, uint64_t m, hipStream_t s) {
+    launch_dict_pack(dg, us, bl, ix, uo, nullptr, n, blob0, (uint32_t)m, dst, s);
+  };
   DictRowSource src;
-  src.write = pack_write;
-  src.arg = &args;
+  src.write = std::ref(write);  // (a reference: no allocation for the captures)
   src.stream = e->fold_stream;
   src.name = "dict_extend_device";
-  src.n = a.n;
-  if (int rc = dict_extend_rows(e, base, src, a.n, nb, false, &d)) return rc;
+  src.n = n;
+  if (int rc = dict_extend_rows(e, base, src, n, nb, false, &d)) return rc;
   *out = d;
   return 0;
 }
+
+static int dict_fold(ngpu_engine *e, ngpu_dict *base, const ngpu_result *d_res,
+                     const ngpu_chunk *d_chunks, uint64_t n, const uint64_t *d_lfirst, uint64_t L,
+                     const ngpu_dict_place *placements, uint64_t n_placements, const uint8_t *blobs,
+                     uint32_t n_blobs, ngpu_dict **out) {
+  if (int rc = dict_plain_base_check(e, base, "dict fold", "node dicts are not supported")) return rc;
+  if (n >= kDictMaxEntries || L >= kDictMaxEntries)
+    return fail(e, NGPU_EINVAL, "dict fold: %llu chunks in %llu layers in one call",
+                (unsigned long long)n, (unsigned long long)L);
+  if (L <= 1) d_lfirst = nullptr, L = 1;  // one layer of n chunks
+  std::lock_guard<std::mutex> lane(e->fold_mu);
+  DeviceGuard dg(e->device);
+  const FoldScratch lay = fold_scratch_layout(n, L, 8 * kFoldCtrWords);
+  if (int rc = fold_lane(e, lay.bytes)) return rc;
+  const hipStream_t s = e->fold_stream;
+  uint8_t *scr = e->fold_scr;
+  uint64_t *d_words = (uint64_t *)(scr + lay.words), *d_sums = (uint64_t *)(scr + lay.sums),
+           *d_ctr = (uint64_t *)(scr + lay.ctr);
+  uint32_t *d_cnt = (uint32_t *)(scr + lay.cnt), *d_rank = (uint32_t *)(scr + lay.rank);
+  uint64_t ctr[kFoldCtrWords] = {};
+  int rc = 0;
+  double pre_us = 0;
+  {
+    DictTrace tr(2);  // launches 1-3
+    if (hipMemsetAsync(d_ctr, 0, 8 * kFoldCtrWords, s) != hipSuccess)
+      rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
+    if (!rc) {
+      tr.record(0, s);
+      launch_fold_keep_scan(d_res, d_chunks, n, e->cfg.chunk_size, d_lfirst, L, d_words, d_cnt, d_sums,
+                            d_rank, d_ctr, s);
+      if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
+      tr.record(1, s);
+    }
+    // k, b and the refusals in one small copy: the call's only mid-way sync
+    if (!rc && (hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess))
+      rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
+    if (!rc) pre_us = std::max(0.0, tr.us(0, 1));
+  }
+  if (rc) return rc;
+  // every check below comes before `used` is reserved or a storage byte is written
+  const FoldVerdict v = fold_counts_verdict(ctr, n, L);
+  if (int r = fold_fail(e, "dict fold: ", v, n, L)) return r;
+  const uint64_t k = v.k, b = v.b;
+  const DictFoldPlace pr =
+      dict_fold_place_rule(base->dev.m, base->has_place, placements != nullptr, n_placements, k);
+  if (int r = fold_place_fail(e, "dict fold: ", pr, n_placements, k, !blobs || n_blobs == b, n_blobs, b))
+    return r;
+  uint32_t nb = 0;
+  bool with_table = false;
+  if (int r = dict_extend_check_blobs(e, base, k, (uint32_t)b, blobs && n_blobs, n_blobs, &nb, &with_table))
+    return r;
+  ngpu_dict *d = nullptr;
+  if (k == 0) {  // a handle equal to base
+    rc = dict_extend_rows(e, base, DictRowSource{}, 0, base->dev.n_blobs, base->has_place, &d);
+  } else {
+    const uint32_t blob0 = base->dev.n_blobs;
+    auto write = [&](DictRec *dst, uint64_t m, hipStream_t ws) {
+      launch_fold_scatter(d_res, d_chunks, n, d_words, d_cnt, d_lfirst, L, d_rank, blob0, (uint32_t)m,
+                          dst, k, ws);
+    };
+    DictRowSource src;
+    src.write = std::ref(write);  // (a reference: no allocation for the captures)
+    src.rows = reinterpret_cast<const DictPlace *>(placements);
+    src.stream = s;
+    src.name = "dict_fold";
+    src.pre_us = (float)pre_us;
+    src.n = n;
+    rc = dict_extend_rows(e, base, src, k, nb, pr == kPlaceKept, &d);
+  }
+  if (rc) return rc;
+  dict_merge_blob_table(d, base, with_table, blobs, n_blobs);
+  *out = d;
+  return 0;
+}
+
+extern "C" {
 
 int ngpu_dict_extend_device(ngpu_engine *e, ngpu_dict *base, const uint8_t *d_digests,
                             const uint32_t *d_usize, const uint32_t *d_blob_index,
@@ -1245,120 +993,9 @@ int ngpu_dict_extend_device(ngpu_engine *e, ngpu_dict *base, const uint8_t *d_di
       ((uintptr_t)d_digests & 15))
     return NGPU_EINVAL;
   return guarded([&] {
-    return dict_extend_device(e, base, PackArgs{d_digests, d_usize, d_blob_index, d_chunk_index, d_uoff, n, 0},
+    return dict_extend_device(e, base, d_digests, d_usize, d_blob_index, d_chunk_index, d_uoff, n,
                               n_blobs, out);
   });
-}
-
-static int dict_fold(ngpu_engine *e, ngpu_dict *base, const ngpu_result *d_res,
-                     const ngpu_chunk *d_chunks, uint64_t n, const uint64_t *d_lfirst, uint64_t L,
-                     const ngpu_dict_place *placements, uint64_t n_placements, const uint8_t *blobs,
-                     uint32_t n_blobs, ngpu_dict **out) {
-  if (int rc = dict_fold_base_check(e, base, "dict fold")) return rc;
-  if (n >= kDictMaxEntries || L >= kDictMaxEntries)
-    return fail(e, NGPU_EINVAL, "dict fold: %llu chunks in %llu layers in one call",
-                (unsigned long long)n, (unsigned long long)L);
-  if (L <= 1) d_lfirst = nullptr, L = 1;  // one layer of n chunks
-  std::lock_guard<std::mutex> lane(e->fold_mu);
-  DeviceGuard dg(e->device);
-  // scratch: keep words, tile sums (+ the total), counters, word counts /
-  // prefixes, layer ranks
-  const uint64_t nw = (n + 63) / 64, nt = dict_retire_scan_tiles(n);
-  const uint64_t o_sums = 8 * nw, o_ctr = o_sums + 8 * (nt + 1), o_cnt = o_ctr + 8 * kFoldCtrWords,
-                 o_rank = o_cnt + 4 * nw, bytes = o_rank + 4 * L;
-  if (int rc = fold_lane(e, bytes)) return rc;
-  const hipStream_t s = e->fold_stream;
-  uint8_t *scr = e->fold_scr;
-  uint64_t *d_words = (uint64_t *)scr, *d_sums = (uint64_t *)(scr + o_sums),
-           *d_ctr = (uint64_t *)(scr + o_ctr);
-  uint32_t *d_cnt = (uint32_t *)(scr + o_cnt), *d_rank = (uint32_t *)(scr + o_rank);
-  static const bool trace = [] {
-    const char *v = getenv("NGPU_DICT_TRACE");
-    return v && v[0] == '1';
-  }();
-  hipEvent_t tev[2] = {};
-  if (trace)
-    for (hipEvent_t &x : tev)
-      if (hipEventCreate(&x) != hipSuccess) x = nullptr;
-  const bool timed = tev[0] && tev[1];
-  uint64_t ctr[kFoldCtrWords] = {};
-  int rc = 0;
-  if (hipMemsetAsync(d_ctr, 0, 8 * kFoldCtrWords, s) != hipSuccess)
-    rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
-  if (!rc) {
-    if (timed) (void)hipEventRecord(tev[0], s);
-    launch_fold_keep_scan(d_res, d_chunks, n, e->cfg.chunk_size, d_lfirst, L, d_words, d_cnt, d_sums,
-                          d_rank, d_ctr, s);
-    if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
-    if (timed) (void)hipEventRecord(tev[1], s);
-  }
-  // k, b and the refusals in one small copy: the call's only mid-way sync
-  if (!rc && (hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, s) != hipSuccess ||
-              hipStreamSynchronize(s) != hipSuccess))
-    rc = fail(e, NGPU_EHIP, "dict fold: keep scan failed");
-  float pre_ms = 0;
-  if (!rc && timed && hipEventElapsedTime(&pre_ms, tev[0], tev[1]) != hipSuccess) pre_ms = 0;
-  for (hipEvent_t x : tev)
-    if (x) (void)hipEventDestroy(x);
-  if (rc) return rc;
-  const uint64_t k = ctr[kFoldK], b = ctr[kFoldBlobs];
-  // every check below comes before `used` is reserved or a storage byte is written
-  if (ctr[kFoldBadLayer1])
-    return fail(e, NGPU_EINVAL,
-                "dict fold: layer_first is not 0 = first[0] <= ... <= first[%llu] = %llu at layer %llu",
-                (unsigned long long)L, (unsigned long long)n,
-                (unsigned long long)~ctr[kFoldBadLayer1]);
-  if (ctr[kFoldBadKind])
-    return fail(e, NGPU_EINVAL,
-                "dict fold: chunk %llu is no dedup result (its kind is none of NEW / INTRA / DICT; "
-                "%llu such chunks)",
-                (unsigned long long)~ctr[kFoldBadKind1], (unsigned long long)ctr[kFoldBadKind]);
-  if (ctr[kFoldBadLen])
-    return fail(e, NGPU_EINVAL,
-                "dict fold: NEW chunk %llu has length 0 or more than chunk size 0x%x (%llu such chunks)",
-                (unsigned long long)~ctr[kFoldBadLen1], e->cfg.chunk_size,
-                (unsigned long long)ctr[kFoldBadLen]);
-  if (k > n || b > L || b > k)
-    return fail(e, NGPU_EHIP, "dict fold: %llu NEW chunks in %llu layers of %llu chunks",
-                (unsigned long long)k, (unsigned long long)b, (unsigned long long)n);
-  const DictFoldPlace pr =
-      dict_fold_place_rule(base->dev.m, base->has_place, placements != nullptr, n_placements, k);
-  if (pr == kPlaceCount)
-    return fail(e, NGPU_EINVAL, "dict fold: %llu placements for %llu NEW chunks",
-                (unsigned long long)n_placements, (unsigned long long)k);
-  if (pr == kPlaceMissing)
-    return fail(e, NGPU_EINVAL, "dict fold: the base keeps compressed placements, the call gives none");
-  if (pr == kPlaceUnwanted)
-    return fail(e, NGPU_EINVAL, "dict fold: the base keeps no compressed placements, the call gives some");
-  if (blobs && n_blobs != b)
-    return fail(e, NGPU_EINVAL, "dict fold: a blob table of %u rows for %llu layers with a NEW chunk",
-                n_blobs, (unsigned long long)b);
-  uint32_t nb = 0;
-  bool with_table = false;
-  if (int r = dict_extend_check_blobs(e, base, k, (uint32_t)b, blobs && n_blobs, n_blobs, &nb, &with_table))
-    return r;
-  ngpu_dict *d = nullptr;
-  if (k == 0) {  // a handle equal to base
-    rc = dict_extend_rows(e, base, DictRowSource{}, 0, base->dev.n_blobs, base->has_place, &d);
-  } else {
-    const FoldArgs args{d_res, d_chunks, n, d_words, d_cnt, d_lfirst, L, d_rank, base->dev.n_blobs, k};
-    DictRowSource src;
-    src.write = fold_write;
-    src.arg = &args;
-    src.rows = reinterpret_cast<const DictPlace *>(placements);
-    src.stream = s;
-    src.name = "dict_fold";
-    src.pre_us = pre_ms * 1000.0f;
-    src.n = n;
-    rc = dict_extend_rows(e, base, src, k, nb, pr == kPlaceKept, &d);
-  }
-  if (rc) return rc;
-  if (with_table) {
-    d->blob_table = base->blob_table;
-    if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
-  }
-  *out = d;
-  return 0;
 }
 
 int ngpu_dict_fold(ngpu_engine *e, ngpu_dict *base, const ngpu_result *d_results,
@@ -1381,12 +1018,9 @@ int ngpu_dict_retire(ngpu_engine *e, ngpu_dict *base, const uint32_t *blobs, uin
   if (out) *out = nullptr;
   if (!base || flags || !e || !out || (n && !blobs)) return NGPU_EINVAL;
   return guarded([&]() -> int {
-    if (!base->parts.empty())
-      return fail(e, NGPU_EINVAL, "dict retire: a node dict is retired with ngpu_node_dict_retire");
-    if (base->device != e->device)
-      return fail(e, NGPU_EINVAL, "chunk dict lives on device %d, engine on %d", base->device,
-                  e->device);
-    if (int rc = dict_check(e, base)) return rc;
+    if (int rc = dict_plain_base_check(e, base, "dict retire",
+                                       "a node dict is retired with ngpu_node_dict_retire"))
+      return rc;
     const DictRetirePlan plan = dict_retire_plan(base->dev.n_blobs, blobs, n);
     if (!plan.ok)
       return fail(e, NGPU_EINVAL, "dict retire: blob %u of a dict of %u blobs", plan.bad,

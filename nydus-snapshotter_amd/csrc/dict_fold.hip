@@ -134,21 +134,6 @@ __global__ __launch_bounds__(256) void fold_scatter(
   }
 }
 
-__global__ void dict_pack_at(const uint8_t *__restrict__ digests, const uint32_t *__restrict__ usize,
-                             const uint32_t *__restrict__ blob, const uint32_t *__restrict__ index,
-                             const uint64_t *__restrict__ uoff, uint64_t n, uint32_t blob0,
-                             uint32_t gid0, DictRec *__restrict__ out) {
-  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint4 *dg = reinterpret_cast<const uint4 *>(digests + 32 * i);
-  uint4 *o = reinterpret_cast<uint4 *>(out + i);
-  o[0] = dg[0];
-  o[1] = dg[1];
-  o[2] = make_uint4(usize[i], blob[i] + blob0, index ? index[i] : 0, gid0 + (uint32_t)i);
-  const uint64_t u = uoff ? uoff[i] : 0;
-  o[3] = make_uint4((uint32_t)u, (uint32_t)(u >> 32), 0, 0);
-}
-
 }  // namespace
 
 void launch_fold_keep_scan(const ngpu_result *res, const ngpu_chunk *chunks, uint64_t n,
@@ -173,14 +158,6 @@ void launch_fold_scatter(const ngpu_result *res, const ngpu_chunk *chunks, uint6
   hipLaunchKernelGGL(fold_scatter, dim3((unsigned)((nw + kFoldWords - 1) / kFoldWords)), dim3(256), 0,
                      s, res, chunks, n, words, prefix, lfirst, lfirst ? L : 1, lrank, blob0, gid0, out,
                      k);
-}
-
-void launch_dict_pack_at(const uint8_t *digests, const uint32_t *usize, const uint32_t *blob,
-                         const uint32_t *index, const uint64_t *uoff, uint64_t n, uint32_t blob0,
-                         uint32_t gid0, DictRec *out, hipStream_t s) {
-  if (n == 0) return;
-  hipLaunchKernelGGL(dict_pack_at, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, digests, usize,
-                     blob, index, uoff, n, blob0, gid0, out);
 }
 
 }  // namespace ngpu

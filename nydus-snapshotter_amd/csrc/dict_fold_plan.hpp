@@ -10,6 +10,8 @@
 
 #include <vector>
 
+#include "dict_retire_plan.hpp"  // the scan tiles of the keep words
+
 namespace ngpu {
 
 // ---- blob table: extend's rule --------------------------------------------------
@@ -49,6 +51,55 @@ inline DictFoldPlace dict_fold_place_rule(uint64_t base_m, bool base_keeps, bool
   if (base_keeps && !given) return kPlaceMissing;
   if (base_m && !base_keeps && given) return kPlaceUnwanted;
   return given ? kPlaceKept : kPlaceNone;
+}
+
+// ---- device scratch and counters ------------------------------------------------
+// ctr: kFoldCtrWords u64 the kernels (dict_fold.hip) fill, zeroed on the fold's
+// stream by the caller before launch_fold_keep_scan.
+constexpr int kFoldK = 0;         // NEW chunks of the call
+constexpr int kFoldBlobs = 1;     // layers with a NEW chunk
+constexpr int kFoldBadKind = 2;   // chunks whose kind is none of NEW / INTRA / DICT
+constexpr int kFoldBadKind1 = 3;  // ~(the smallest such chunk id) (atomic max), 0 = none
+constexpr int kFoldBadLen = 4;    // NEW chunks of length 0 or > chunk_size
+constexpr int kFoldBadLen1 = 5;   // ~(the smallest such chunk id), 0 = none
+constexpr int kFoldBadLayer1 = 6; // ~(the smallest layer whose bounds are out of order), 0 = none
+constexpr int kFoldCtrWords = 8;
+
+// A fold's scratch, byte offsets: keep words (u64 per 64 chunks, at 0), tile sums
+// + the total (u64), ctr_bytes of counters (u64; a node fold's are followed by
+// its owner counts), word counts / prefixes (u32), L layer ranks (u32).
+struct FoldScratch { uint64_t words = 0, sums = 0, ctr = 0, cnt = 0, rank = 0, bytes = 0; };
+inline FoldScratch fold_scratch_layout(uint64_t n, uint64_t L, uint64_t ctr_bytes) {
+  const uint64_t nw = (n + 63) / 64;
+  FoldScratch s;
+  s.sums = 8 * nw;
+  s.ctr = s.sums + 8 * (dict_retire_scan_tiles(n) + 1);
+  s.cnt = s.ctr + ctr_bytes;
+  s.rank = s.cnt + 4 * nw;
+  s.bytes = s.rank + 4 * L;
+  return s;
+}
+
+// What the counters of a fold over n chunks in L layers say: the first refusal in
+// the order layer cut, kind, length, then counts no table can give.
+struct FoldVerdict {
+  enum Why { ok, bad_layer, bad_kind, bad_len, insane } why = ok;
+  uint64_t k = 0, b = 0;          // NEW chunks; layers with one
+  uint64_t which = 0, count = 0;  // the first bad layer / chunk; how many such chunks
+};
+inline FoldVerdict fold_counts_verdict(const uint64_t *ctr, uint64_t n, uint64_t L) {
+  FoldVerdict v;
+  v.k = ctr[kFoldK];
+  v.b = ctr[kFoldBlobs];
+  if (ctr[kFoldBadLayer1])
+    v.why = FoldVerdict::bad_layer, v.which = ~ctr[kFoldBadLayer1];
+  else if (ctr[kFoldBadKind])
+    v.why = FoldVerdict::bad_kind, v.which = ~ctr[kFoldBadKind1], v.count = ctr[kFoldBadKind];
+  else if (ctr[kFoldBadLen])
+    v.why = FoldVerdict::bad_len, v.which = ~ctr[kFoldBadLen1], v.count = ctr[kFoldBadLen];
+  else if (v.k > n || v.b > L || v.b > v.k)
+    v.why = FoldVerdict::insane;
+  return v;
 }
 
 // ---- what the kernels compute ---------------------------------------------------

@@ -111,11 +111,6 @@ __global__ __launch_bounds__(256) void dict_compact(const DictRec *__restrict__ 
 
 }  // namespace
 
-uint64_t dict_retire_scan_tiles(uint64_t m) {
-  const uint64_t nw = (m + 63) / 64;
-  return (nw + kRetireScanTile - 1) / kRetireScanTile;
-}
-
 void launch_dict_keep_scan(const DictRec *rec, uint64_t m, const uint32_t *bitmap, uint32_t n_blobs,
                            uint64_t *words, uint32_t *cnt, uint64_t *sums, hipStream_t s) {
   if (m)

@@ -84,4 +84,26 @@ inline void dict_retire_compact_rows(const uint64_t *words, const uint32_t *pref
 }
 constexpr uint64_t kRetireHostPiece = 4096;  // keep words per host work item: 262,144 rows
 
+// ---- device scratch ---------------------------------------------------------------
+// One scan tile (dict_retire.hip) is kRetireScanTile keep words: 16,384 records.
+constexpr uint64_t kRetireScanTile = 256;
+inline uint64_t dict_retire_scan_tiles(uint64_t m) {
+  return ((m + 63) / 64 + kRetireScanTile - 1) / kRetireScanTile;
+}
+
+// A retire's one scratch allocation, byte offsets: keep words (u64 per 64
+// records, at 0), tile sums + the total (u64), word counts / prefixes (u32), the
+// retire bitmap and the blob remap (u32 each).
+struct RetireScratch { uint64_t words = 0, sums = 0, cnt = 0, bits = 0, remap = 0, bytes = 0; };
+inline RetireScratch retire_scratch_layout(uint64_t m, uint64_t bitmap_words, uint64_t remap_words) {
+  const uint64_t nw = (m + 63) / 64;
+  RetireScratch s;
+  s.sums = 8 * nw;
+  s.cnt = s.sums + 8 * (dict_retire_scan_tiles(m) + 1);
+  s.bits = s.cnt + 4 * nw;
+  s.remap = s.bits + 4 * bitmap_words;
+  s.bytes = s.remap + 4 * remap_words;
+  return s;
+}
+
 }  // namespace ngpu

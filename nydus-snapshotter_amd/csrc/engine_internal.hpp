@@ -4,6 +4,7 @@
 #pragma once
 
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -352,6 +353,34 @@ int dict_check(ngpu_engine *e, const ngpu_dict *d);
 ngpu_dict *default_dict(ngpu_engine *e);
 inline uint32_t dict_blobs(const ngpu_dict *d) { return d ? d->dev.n_blobs : 0; }
 uint64_t next_pow2(uint64_t x);
+// Dict uploads and table builds run on a stream of their own, outside the engine lock.
+struct BuildStream {
+  hipStream_t s = nullptr;
+  explicit BuildStream(int device);
+  ~BuildStream();
+};
+// A new handle for engine e, or one like base (device, digester, chunk size, node mode).
+ngpu_dict *dict_new(ngpu_engine *e);
+ngpu_dict *dict_derive(const ngpu_dict *base);
+// An m-entry dict's own storage, all of it reserved; the table over its uploaded records.
+int dict_alloc(ngpu_engine *e, ngpu_dict *d, uint64_t m, uint32_t n_blobs, bool place);
+int dict_build(ngpu_engine *e, ngpu_dict *d, hipStream_t s);
+// dst[0, k) = the compressed placements of k 80-B records.
+void place_rows_from_records(const uint8_t *recs, uint64_t k, DictPlace *dst);
+// *nb = the blobs k host records name (n_blobs when given), or the refusal: a record
+// past n_blobs, an index past 2^20.  blob_count_verdict: its last step alone.
+int records_blob_count(ngpu_engine *e, const uint8_t *recs, uint64_t k, uint32_t n_blobs,
+                       uint32_t *nb);
+int blob_count_verdict(ngpu_engine *e, uint64_t seen, uint32_t n_blobs, uint32_t *nb);
+// d's blob table when the result keeps one (with_table): base's rows ++ the call's.
+void dict_merge_blob_table(ngpu_dict *d, const ngpu_dict *base, bool with_table,
+                           const uint8_t *blobs, uint32_t n_blobs);
+// base is a plain dict of engine e's device (node_hint: what to say of a node dict).
+int dict_plain_base_check(ngpu_engine *e, const ngpu_dict *base, const char *what,
+                          const char *node_hint);
+// ngpu_dict_extend's body (dict_load.hip extends by a bootstrap's records).
+int dict_extend(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, uint64_t n,
+                const uint8_t *blobs, uint32_t n_blobs, ngpu_dict **out);
 // From 80-B RAFS v6 records in host memory on engine e's device (own stream, no lock).
 int dict_from_records(ngpu_engine *e, const uint8_t *recs, uint64_t m, const uint8_t *blobs,
                       uint32_t n_blobs, ngpu_dict **out, const uint32_t *gids);
@@ -374,15 +403,14 @@ int dict_extend_records(ngpu_engine *e, ngpu_dict *base, const uint8_t *recs, ui
 // Where the k new records of an extend come from.  Either 80-B records in host
 // memory (recs: uploaded through a staging buffer and unpacked, placements read
 // from them), or a kernel that writes rec[m, m + k) from what already lies in
-// HBM (write: enqueue it on s; dst = the result's rec + m; no staging buffer),
-// with the placement rows, if the result keeps any, in `rows`.  The share / fork
+// HBM (write: enqueue it on s; dst = the result's rec + m of m base entries; no
+// staging buffer), with the placement rows, if the result keeps any, in `rows`.  The share / fork
 // decision, the storage and the handle are the same for both (dict_extend_rows).
 struct DictRowSource {
   const uint8_t *recs = nullptr;   // host 80-B records, or
   const uint32_t *gids = nullptr;  //   (their global ids, null = m + position)
   uint32_t blob0 = 0;              //   (added to their blob indices)
-  void (*write)(const DictRowSource &src, DictRec *dst, uint64_t m, hipStream_t s) = nullptr;
-  const void *arg = nullptr;       // write's own
+  std::function<void(DictRec *dst, uint64_t m, hipStream_t s)> write;
   const DictPlace *rows = nullptr; // device source: k placement rows (host), null = none
   hipStream_t stream = nullptr;    // device source: the stream its inputs are ordered on
   const char *name = "dict_extend"; // NGPU_DICT_TRACE line
@@ -400,6 +428,15 @@ int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const DictPlace *rows, ui
 // e->fold_mu held: the engine's fold stream, and at least `bytes` of fold_scr
 // (dict.hip; grown only while nothing of an earlier fold still runs).
 int fold_lane(ngpu_engine *e, uint64_t bytes);
+// A kept device buffer of at least `bytes`, grown by half again (msg: the refusal).
+int grow_kept(ngpu_engine *e, uint8_t **ptr, uint64_t *cap, uint64_t bytes, const char *msg);
+// A storage of `cap` placement rows and nothing else (node dicts' global handles).
+int storage_alloc_place_only(ngpu_engine *e, uint64_t cap, DictStorage **out);
+// The refusals of a fold's counters, of its placement rule and of its blob table's
+// row count, after `prefix` ("dict fold: ", "node dict fold: part 3: "); 0: none.
+int fold_fail(ngpu_engine *e, const char *prefix, const FoldVerdict &v, uint64_t n, uint64_t L);
+int fold_place_fail(ngpu_engine *e, const char *prefix, DictFoldPlace pr, uint64_t n_placements,
+                    uint64_t k, bool rows_ok, uint32_t n_blobs, uint64_t b);
 void storage_unref(DictStorage *st);
 // Dict retire (dict.hip): a new handle, on a storage of its own, of base's own
 // records whose blob bitmap bit is clear, blob indices through remap (both

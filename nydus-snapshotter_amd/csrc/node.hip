@@ -251,6 +251,31 @@ int node_dict_hits(ngpu_engine *e, ngpu_dict *d, const uint8_t *digests, uint64_
 
 namespace {
 
+// base is a dict of this node: one part per device, in the node's order, and
+// usable by its engines.  what: "extend", "retire", "fold".
+int node_dict_base_check(ngpu_node *node, const ngpu_dict *base, const char *what) {
+  ngpu_engine *e0 = node->eng[0];
+  const uint32_t W = (uint32_t)node->eng.size();
+  if (base->parts.empty())
+    return fail(e0, NGPU_EINVAL, "node dict %s: not a node dict (ngpu_dict_%s takes it)", what, what);
+  bool ours = base->parts.size() == W;
+  for (uint32_t o = 0; ours && o < W; ++o) ours = base->parts[o]->device == node->eng[o]->device;
+  if (!ours) return fail(e0, NGPU_EINVAL, "node dict %s: dict of another node", what);
+  return dict_check(e0, base);
+}
+
+// k host records by owner part, in table order, with their global ids gid0 + position
+// (part_recs, gid: W empty vectors).
+void node_partition_records(const uint8_t *recs, uint64_t k, uint32_t W, uint64_t gid0,
+                            std::vector<std::vector<uint8_t>> *part_recs,
+                            std::vector<std::vector<uint32_t>> *gid) {
+  for (uint64_t i = 0; i < k; ++i) {
+    const uint32_t o = owner_of(recs + 80 * i, W);
+    (*part_recs)[o].insert((*part_recs)[o].end(), recs + 80 * i, recs + 80 * (i + 1));
+    (*gid)[o].push_back((uint32_t)(gid0 + i));
+  }
+}
+
 // A node dict over records in host memory (each part built on its device's
 // own build stream, no engine lock held).
 int node_dict_build(ngpu_node *node, const uint8_t *recs, uint64_t m, const uint8_t *blobs,
@@ -264,19 +289,8 @@ int node_dict_build(ngpu_node *node, const uint8_t *recs, uint64_t m, const uint
     return fail(e0, NGPU_EINVAL, "bad node dict mode %u", mode);
   if (m >= 0xFFFFFFFFull) return fail(e0, NGPU_EINVAL, "chunk dict too large");
   uint32_t nb = 0;
-  for (uint64_t i = 0; i < m; ++i) {
-    const RafsV6ChunkInfo *r = reinterpret_cast<const RafsV6ChunkInfo *>(recs + 80 * i);
-    nb = std::max(nb, r->blob_index + 1);
-  }
-  if (n_blobs) {
-    if (nb > n_blobs) return fail(e0, NGPU_EFORMAT, "chunk dict record points at blob %u of %u",
-                                  nb - 1, n_blobs);
-    nb = n_blobs;
-  }
-  ngpu_dict *d = new ngpu_dict();
-  d->device = node->dev[0];
-  d->digester = e0->cfg.digester;
-  d->chunk_size = e0->cfg.chunk_size;
+  if (int rc = records_blob_count(e0, recs, m, n_blobs, &nb)) return rc;
+  ngpu_dict *d = dict_new(e0);
   d->replicated = mode == NGPU_NODE_DICT_REPLICATE;
   // the copy exchange (DMA peer copies) unless the routed one was asked for
   // and every pair of devices has peer access (its kernels reach the
@@ -295,13 +309,7 @@ int node_dict_build(ngpu_node *node, const uint8_t *recs, uint64_t m, const uint
   // partition: rows per owner in global table order, with their global ids
   std::vector<std::vector<uint8_t>> part_recs(W);
   std::vector<std::vector<uint32_t>> gid(W);
-  if (!d->replicated) {
-    for (uint64_t i = 0; i < m; ++i) {
-      const uint32_t o = owner_of(recs + 80 * i, W);
-      part_recs[o].insert(part_recs[o].end(), recs + 80 * i, recs + 80 * (i + 1));
-      gid[o].push_back((uint32_t)i);
-    }
-  }
+  if (!d->replicated) node_partition_records(recs, m, W, 0, &part_recs, &gid);
   int rc = 0;
   for (uint32_t o = 0; o < W && !rc; ++o) {
     ngpu_engine *e = node->eng[o];
@@ -334,35 +342,18 @@ int node_dict_extend(ngpu_node *node, ngpu_dict *base, const uint8_t *recs, uint
                      const uint8_t *blobs, uint32_t n_blobs, ngpu_dict **out) {
   ngpu_engine *e0 = node->eng[0];
   const uint32_t W = (uint32_t)node->eng.size();
-  if (base->parts.empty())
-    return fail(e0, NGPU_EINVAL, "node dict extend: not a node dict (ngpu_dict_extend takes it)");
-  if (base->parts.size() != W) return fail(e0, NGPU_EINVAL, "node dict extend: dict of another node");
-  for (uint32_t o = 0; o < W; ++o)
-    if (base->parts[o]->device != node->eng[o]->device)
-      return fail(e0, NGPU_EINVAL, "node dict extend: dict of another node");
-  if (int rc = dict_check(e0, base)) return rc;
+  if (int rc = node_dict_base_check(node, base, "extend")) return rc;
   uint32_t nb = 0;
   bool with_table = false;
   if (int rc = dict_extend_check(e0, base, recs, k, blobs, n_blobs, &nb, &with_table)) return rc;
   const uint64_t m = base->dev.m;
-  ngpu_dict *d = new ngpu_dict();
-  d->device = base->device;
-  d->digester = base->digester;
-  d->chunk_size = base->chunk_size;
-  d->replicated = base->replicated;
-  d->routed = base->routed;
+  ngpu_dict *d = dict_derive(base);
   d->dev.m = m + k;
   d->dev.n_blobs = nb;
   int rc = dict_place_extend(e0, base, recs, k, d);
   std::vector<std::vector<uint8_t>> part_recs(W);
   std::vector<std::vector<uint32_t>> gid(W);
-  if (!rc && !d->replicated) {
-    for (uint64_t i = 0; i < k; ++i) {
-      const uint32_t o = owner_of(recs + 80 * i, W);
-      part_recs[o].insert(part_recs[o].end(), recs + 80 * i, recs + 80 * (i + 1));
-      gid[o].push_back((uint32_t)(m + i));
-    }
-  }
+  if (!rc && !d->replicated) node_partition_records(recs, k, W, m, &part_recs, &gid);
   for (uint32_t o = 0; o < W && !rc; ++o) {
     ngpu_dict *p = nullptr;
     const uint8_t *pr = d->replicated ? recs : part_recs[o].data();
@@ -376,10 +367,7 @@ int node_dict_extend(ngpu_node *node, ngpu_dict *base, const uint8_t *recs, uint
     dict_unref(d);
     return rc;
   }
-  if (with_table) {
-    d->blob_table = base->blob_table;
-    if (blobs && n_blobs) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
-  }
+  dict_merge_blob_table(d, base, with_table, blobs, n_blobs);
   *out = d;
   return 0;
 }
@@ -392,13 +380,7 @@ int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, ui
                      ngpu_dict **out) {
   ngpu_engine *e0 = node->eng[0];
   const uint32_t W = (uint32_t)node->eng.size();
-  if (base->parts.empty())
-    return fail(e0, NGPU_EINVAL, "node dict retire: not a node dict (ngpu_dict_retire takes it)");
-  if (base->parts.size() != W) return fail(e0, NGPU_EINVAL, "node dict retire: dict of another node");
-  for (uint32_t o = 0; o < W; ++o)
-    if (base->parts[o]->device != node->eng[o]->device)
-      return fail(e0, NGPU_EINVAL, "node dict retire: dict of another node");
-  if (int rc = dict_check(e0, base)) return rc;
+  if (int rc = node_dict_base_check(node, base, "retire")) return rc;
   const DictRetirePlan plan = dict_retire_plan(base->dev.n_blobs, blobs, n);
   if (!plan.ok)
     return fail(e0, NGPU_EINVAL, "node dict retire: blob %u of a dict of %u blobs", plan.bad,
@@ -406,12 +388,7 @@ int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, ui
   if (!base->replicated)
     return fail(e0, NGPU_EUNSUPP,
                 "node dict retire: partitioned node dicts are not supported yet (replicated ones are)");
-  ngpu_dict *d = new ngpu_dict();
-  d->device = base->device;
-  d->digester = base->digester;
-  d->chunk_size = base->chunk_size;
-  d->replicated = true;
-  d->routed = base->routed;
+  ngpu_dict *d = dict_derive(base);
   DictKeep keep;
   int rc = 0;
   for (uint32_t o = 0; o < W && !rc; ++o) {
@@ -430,20 +407,14 @@ int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, ui
     const uint64_t m = base->dev.m, s = d->parts[0]->dev.m;
     d->dev.m = s;
     d->dev.n_blobs = plan.n_kept;
-    // the global handle: placement rows only, with a fork's room
-    DictStorage *st = new DictStorage();
-    st->device = e0->device;
-    st->rec_cap = dict_retire_rec_cap(s);
-    st->table_cap = ~0ull;
-    st->used = s;
-    d->st = st;
+    // the global handle: placement rows only (if base keeps any), with a fork's room
     const DictPlace *rows = base->place();
-    if (rows && s) {
-      if (!(st->place = (DictPlace *)malloc(st->rec_cap * sizeof(DictPlace)))) {
-        rc = fail(e0, NGPU_ENOMEM, "chunk dict: no host memory for %llu placement rows",
-                  (unsigned long long)st->rec_cap);
-      } else {
-        dict_retire_place(keep, m, rows, st->place, s);
+    const uint64_t cap = dict_retire_rec_cap(s);
+    if (!(rc = storage_alloc_place_only(e0, rows && s ? cap : 0, &d->st))) {
+      d->st->rec_cap = cap;
+      d->st->used = s;
+      if (rows && s) {
+        dict_retire_place(keep, m, rows, d->st->place, s);
         d->has_place = true;
       }
     }
@@ -480,33 +451,28 @@ int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, ui
 //   f. the global handle's placement rows and blob table, as node_dict_extend.
 struct NodeFoldRows {
   uint8_t *scr = nullptr;  // engine i's fold_scr
-  uint64_t o_sums = 0, o_ctr = 0, o_cnt = 0, o_rank = 0;
+  FoldScratch lay;
   DictRec *staged = nullptr, *split = nullptr;
   uint32_t *tcnt = nullptr;
   uint64_t *tsums = nullptr;
 };
 constexpr uint64_t kNodeFoldCtrBytes = 8 * kFoldCtrWords + 4 * kNodeFoldMaxParts;  // counters + owner counts
 
-struct NodeFoldCopy {
-  ngpu_node *node;
-  const NodeFoldPlan *plan;
-  const std::vector<NodeFoldRows> *rows;
-  const uint32_t *c;  // W x W owner counts, null: replicated
-  uint32_t W, o;
-};
-void node_fold_write(const DictRowSource &src, DictRec *dst, uint64_t, hipStream_t s) {
-  const NodeFoldCopy &a = *static_cast<const NodeFoldCopy *>(src.arg);
-  const uint32_t W = a.W, o = a.o;
+// Part o's new rows into dst on s, in source order.  c: W x W owner counts (a
+// partition takes its W segments), null: a replica takes all W staging areas.
+void node_fold_write(ngpu_node *node, const NodeFoldPlan &plan, const std::vector<NodeFoldRows> &rows,
+                     const uint32_t *c, uint32_t o, DictRec *dst, hipStream_t s) {
+  const uint32_t W = (uint32_t)node->eng.size();
   for (uint32_t i = 0; i < W; ++i) {
-    const uint64_t cnt = a.c ? a.c[(size_t)i * W + o] : a.plan->off[i + 1] - a.plan->off[i];
+    const uint64_t cnt = c ? c[(size_t)i * W + o] : plan.off[i + 1] - plan.off[i];
     if (!cnt) continue;
-    const NodeFoldRows &r = (*a.rows)[i];
-    const DictRec *from = a.c ? r.split + a.plan->src[(size_t)i * W + o] : r.staged;
-    DictRec *to = dst + (a.c ? a.plan->dst[(size_t)i * W + o] : a.plan->off[i]);
+    const NodeFoldRows &r = rows[i];
+    const DictRec *from = c ? r.split + plan.src[(size_t)i * W + o] : r.staged;
+    DictRec *to = dst + (c ? plan.dst[(size_t)i * W + o] : plan.off[i]);
     if (i == o) {  // staged on this very stream
       (void)hipMemcpyAsync(to, from, cnt * sizeof(DictRec), hipMemcpyDeviceToDevice, s);
-    } else if (hipStreamWaitEvent(s, a.node->eng[i]->fold_ev, 0) == hipSuccess) {
-      (void)hipMemcpyPeerAsync(to, a.node->dev[o], from, a.node->dev[i], cnt * sizeof(DictRec), s);
+    } else if (hipStreamWaitEvent(s, node->eng[i]->fold_ev, 0) == hipSuccess) {
+      (void)hipMemcpyPeerAsync(to, node->dev[o], from, node->dev[i], cnt * sizeof(DictRec), s);
     }
   }
 }
@@ -523,20 +489,8 @@ int node_fold_lane(ngpu_engine *e, uint64_t bytes) {
     e->fold_ev = nullptr;
     return fail(e, NGPU_EHIP, "node dict fold: event on device %d", e->device);
   }
-  if (bytes > e->fold_rows_cap) {
-    // (nothing of an earlier fold still runs: each is complete when it returns)
-    if (e->fold_rows) (void)hipFree(e->fold_rows);
-    e->fold_rows = nullptr;
-    e->fold_rows_cap = 0;
-    const uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 1u << 16);
-    if (hipMalloc((void **)&e->fold_rows, want) != hipSuccess) {
-      (void)hipGetLastError();
-      e->fold_rows = nullptr;
-      return fail(e, NGPU_ENOMEM, "node dict fold: staging allocation failed");
-    }
-    e->fold_rows_cap = want;
-  }
-  return 0;
+  return grow_kept(e, &e->fold_rows, &e->fold_rows_cap, bytes,
+                   "node dict fold: staging allocation failed");
 }
 
 int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *pt, uint32_t np,
@@ -546,13 +500,7 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
   const uint32_t W = (uint32_t)node->eng.size();
   if (np != W)
     return fail(e0, NGPU_EINVAL, "node dict fold: %u parts for a node of %u devices", np, W);
-  if (base->parts.empty())
-    return fail(e0, NGPU_EINVAL, "node dict fold: not a node dict (ngpu_dict_fold takes it)");
-  if (base->parts.size() != W) return fail(e0, NGPU_EINVAL, "node dict fold: dict of another node");
-  for (uint32_t o = 0; o < W; ++o)
-    if (base->parts[o]->device != node->eng[o]->device)
-      return fail(e0, NGPU_EINVAL, "node dict fold: dict of another node");
-  if (int rc = dict_check(e0, base)) return rc;
+  if (int rc = node_dict_base_check(node, base, "fold")) return rc;
   std::vector<uint64_t> L(W);
   std::vector<const uint64_t *> lfirst(W);
   for (uint32_t i = 0; i < W; ++i) {
@@ -580,17 +528,14 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
     const ngpu_node_fold_part &p = pt[i];
     NodeFoldRows &r = rows[i];
     DeviceGuard dg(e->device);
-    const uint64_t n = p.n, nw = (n + 63) / 64, nt = dict_retire_scan_tiles(n);
-    r.o_sums = 8 * nw;
-    r.o_ctr = r.o_sums + 8 * (nt + 1);
-    r.o_cnt = r.o_ctr + kNodeFoldCtrBytes;
-    r.o_rank = r.o_cnt + 4 * nw;
+    const uint64_t n = p.n;
+    r.lay = fold_scratch_layout(n, L[i], kNodeFoldCtrBytes);
     // the staging areas for the worst case k = n, before the keep words exist
     const uint64_t tw = (uint64_t)W * node_split_tiles(n);
     const uint64_t o_split = n * sizeof(DictRec), o_tcnt = 2 * o_split,
                    o_tsums = (o_tcnt + 4 * tw + 7) & ~7ull,
                    bytes = split ? o_tsums + 8 * ((tw + kRetireScanTile - 1) / kRetireScanTile + 1) : o_split;
-    if ((rc = fold_lane(e, r.o_rank + 4 * L[i])) || (rc = node_fold_lane(e, bytes))) {
+    if ((rc = fold_lane(e, r.lay.bytes)) || (rc = node_fold_lane(e, bytes))) {
       rc = fail(e0, rc, "%s", ngpu_last_error(e));
       break;
     }
@@ -602,12 +547,12 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
       r.tsums = (uint64_t *)(e->fold_rows + o_tsums);
     }
     const hipStream_t s = e->fold_stream;
-    uint64_t *d_ctr = (uint64_t *)(r.scr + r.o_ctr);
+    uint64_t *d_ctr = (uint64_t *)(r.scr + r.lay.ctr);
     bool ok = hipMemsetAsync(d_ctr, 0, kNodeFoldCtrBytes, s) == hipSuccess;
     if (ok) {
       launch_fold_keep_scan(p.d_results, p.d_chunks, n, e->cfg.chunk_size, lfirst[i], L[i],
-                            (uint64_t *)r.scr, (uint32_t *)(r.scr + r.o_cnt),
-                            (uint64_t *)(r.scr + r.o_sums), (uint32_t *)(r.scr + r.o_rank), d_ctr, s);
+                            (uint64_t *)(r.scr + r.lay.words), (uint32_t *)(r.scr + r.lay.cnt),
+                            (uint64_t *)(r.scr + r.lay.sums), (uint32_t *)(r.scr + r.lay.rank), d_ctr, s);
       if (split) launch_fold_owner_counts(p.d_results, n, W, (uint32_t *)(d_ctr + kFoldCtrWords), s);
       ok = hipGetLastError() == hipSuccess &&
            hipMemcpyAsync(e->fold_h, d_ctr, kNodeFoldCtrBytes, hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -628,28 +573,12 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
   for (uint32_t i = 0; i < W; ++i) {
     const uint64_t *ctr = node->eng[i]->fold_h;
     const uint64_t n = pt[i].n;
-    if (ctr[kFoldBadLayer1])
-      return fail(e0, NGPU_EINVAL,
-                  "node dict fold: part %u: layer_first is not 0 = first[0] <= ... <= first[%llu] = %llu "
-                  "at layer %llu",
-                  i, (unsigned long long)L[i], (unsigned long long)n,
-                  (unsigned long long)~ctr[kFoldBadLayer1]);
-    if (ctr[kFoldBadKind])
-      return fail(e0, NGPU_EINVAL,
-                  "node dict fold: part %u: chunk %llu is no dedup result (its kind is none of NEW / "
-                  "INTRA / DICT; %llu such chunks)",
-                  i, (unsigned long long)~ctr[kFoldBadKind1], (unsigned long long)ctr[kFoldBadKind]);
-    if (ctr[kFoldBadLen])
-      return fail(e0, NGPU_EINVAL,
-                  "node dict fold: part %u: NEW chunk %llu has length 0 or more than chunk size 0x%x "
-                  "(%llu such chunks)",
-                  i, (unsigned long long)~ctr[kFoldBadLen1], e0->cfg.chunk_size,
-                  (unsigned long long)ctr[kFoldBadLen]);
-    k[i] = ctr[kFoldK];
-    b[i] = ctr[kFoldBlobs];
-    if (k[i] > n || b[i] > L[i] || b[i] > k[i])
-      return fail(e0, NGPU_EHIP, "node dict fold: part %u: %llu NEW chunks in %llu layers of %llu chunks",
-                  i, (unsigned long long)k[i], (unsigned long long)b[i], (unsigned long long)n);
+    const FoldVerdict v = fold_counts_verdict(ctr, n, L[i]);
+    char prefix[40];
+    snprintf(prefix, sizeof prefix, "node dict fold: part %u: ", i);
+    if (int r = fold_fail(e0, prefix, v, n, L[i])) return r;
+    k[i] = v.k;
+    b[i] = v.b;
     if (split) memcpy(&c[(size_t)i * W], ctr + kFoldCtrWords, 4 * W);
   }
   const NodeFoldPlan plan = node_fold_plan(W, k.data(), b.data(), split ? c.data() : nullptr);
@@ -660,16 +589,9 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
   const bool call_table = blobs && n_blobs;
   const DictFoldPlace pr =
       node_fold_place_rule(m, base->has_place, placements != nullptr, n_placements, plan);
-  if (pr == kPlaceCount)
-    return fail(e0, NGPU_EINVAL, "node dict fold: %llu placements for %llu NEW chunks",
-                (unsigned long long)n_placements, (unsigned long long)K);
-  if (pr == kPlaceMissing)
-    return fail(e0, NGPU_EINVAL, "node dict fold: the base keeps compressed placements, the call gives none");
-  if (pr == kPlaceUnwanted)
-    return fail(e0, NGPU_EINVAL, "node dict fold: the base keeps no compressed placements, the call gives some");
-  if (!node_fold_table_rows_ok(blobs != nullptr, n_blobs, plan))
-    return fail(e0, NGPU_EINVAL, "node dict fold: a blob table of %u rows for %llu layers with a NEW chunk",
-                n_blobs, (unsigned long long)plan.B);
+  if (int r = fold_place_fail(e0, "node dict fold: ", pr, n_placements, K,
+                              node_fold_table_rows_ok(blobs != nullptr, n_blobs, plan), n_blobs, plan.B))
+    return r;
   // (over the untruncated sums: dict_extend_check_blobs below takes a 32-bit blob count)
   const NodeFoldLimit lim = node_fold_limits(m, base->dev.n_blobs, K, plan.B);
   if (lim == kNodeFoldEntries)
@@ -690,9 +612,9 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
     const NodeFoldRows &r = rows[i];
     DeviceGuard dg(e->device);
     const hipStream_t s = e->fold_stream;
-    launch_fold_scatter(p.d_results, p.d_chunks, p.n, (const uint64_t *)r.scr,
-                        (const uint32_t *)(r.scr + r.o_cnt), lfirst[i], L[i],
-                        (const uint32_t *)(r.scr + r.o_rank), base->dev.n_blobs + (uint32_t)plan.boff[i],
+    launch_fold_scatter(p.d_results, p.d_chunks, p.n, (const uint64_t *)(r.scr + r.lay.words),
+                        (const uint32_t *)(r.scr + r.lay.cnt), lfirst[i], L[i],
+                        (const uint32_t *)(r.scr + r.lay.rank), base->dev.n_blobs + (uint32_t)plan.boff[i],
                         (uint32_t)(m + plan.off[i]), r.staged, k[i], s);
     if (split) launch_node_split(r.staged, k[i], W, r.tcnt, r.tsums, r.split, s);
     if (hipGetLastError() != hipSuccess || hipEventRecord(e->fold_ev, s) != hipSuccess) {
@@ -712,12 +634,7 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
   }
 
   // e, f. the handle: placement rows, every part's extend, the blob table
-  ngpu_dict *d = new ngpu_dict();
-  d->device = base->device;
-  d->digester = base->digester;
-  d->chunk_size = base->chunk_size;
-  d->replicated = base->replicated;
-  d->routed = base->routed;
+  ngpu_dict *d = dict_derive(base);
   d->dev.m = m + K;
   d->dev.n_blobs = nb;
   if (pr == kPlaceKept || K == 0)
@@ -725,11 +642,12 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
   for (uint32_t o = 0; o < W && !rc; ++o) {
     ngpu_dict *p = nullptr;
     const uint64_t pk = split ? plan.total[o] : K;
-    const NodeFoldCopy args{node, &plan, &rows, split ? c.data() : nullptr, W, o};
+    auto write = [&](DictRec *dst, uint64_t, hipStream_t s) {
+      node_fold_write(node, plan, rows, split ? c.data() : nullptr, o, dst, s);
+    };
     DictRowSource src;
     if (pk) {
-      src.write = node_fold_write;
-      src.arg = &args;
+      src.write = std::ref(write);  // (a reference: no allocation for the captures)
       src.stream = node->eng[o]->fold_stream;
       src.name = "node_dict_fold";
       src.n = pt[o].n;
@@ -745,10 +663,7 @@ int node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *
     dict_unref(d);
     return rc;
   }
-  if (with_table) {
-    d->blob_table = base->blob_table;
-    if (call_table) d->blob_table.insert(d->blob_table.end(), blobs, blobs + 256ull * n_blobs);
-  }
+  dict_merge_blob_table(d, base, with_table, blobs, n_blobs);
   *out = d;
   return 0;
 }

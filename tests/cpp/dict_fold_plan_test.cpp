@@ -171,6 +171,56 @@ int main() {
     REQUIRE(DictFoldMap::layer_of(first, 4, 2) == 0 && DictFoldMap::layer_of(first, 4, 3) == 2 &&
             DictFoldMap::layer_of(first, 4, 5) == 3);
   }
+  // ---- the scratch layout: the offsets written out by hand ----
+  for (uint64_t n : {0ull, 1ull, 63ull, 64ull, 65ull, 16383ull, 16384ull, 16385ull})
+    for (uint64_t L : {1ull, 2ull, 1000ull})
+      for (uint64_t cb : {8ull * kFoldCtrWords, 8ull * kFoldCtrWords + 4 * 64}) {  // dict fold's, node fold's
+        const uint64_t nw = (n + 63) / 64, nt = (nw + 255) / 256;
+        const FoldScratch s = fold_scratch_layout(n, L, cb);
+        REQUIRE(dict_retire_scan_tiles(n) == nt);
+        REQUIRE(s.words == 0 && s.sums == 8 * nw && s.ctr == 8 * nw + 8 * (nt + 1));
+        REQUIRE(s.cnt == 8 * nw + 8 * (nt + 1) + cb && s.rank == 8 * nw + 8 * (nt + 1) + cb + 4 * nw);
+        REQUIRE(s.bytes == 8 * nw + 8 * (nt + 1) + cb + 4 * nw + 4 * L);
+        REQUIRE(s.words % 8 == 0 && s.sums % 8 == 0 && s.ctr % 8 == 0 && s.cnt % 4 == 0 && s.rank % 4 == 0);
+        REQUIRE(s.words + 8 * nw <= s.sums && s.sums + 8 * (nt + 1) <= s.ctr && s.ctr + cb <= s.cnt &&
+                s.cnt + 4 * nw <= s.rank && s.rank + 4 * L <= s.bytes);
+      }
+  // ---- the counters' verdict: layer, then kind, then length, then insane ----
+  {
+    const uint64_t n = 100, L = 7;
+    auto ctr_of = [](uint64_t k, uint64_t b, bool layer, bool kind, bool len) {
+      std::vector<uint64_t> c(kFoldCtrWords, 0);
+      c[kFoldK] = k, c[kFoldBlobs] = b;
+      if (layer) c[kFoldBadLayer1] = ~5ull;
+      if (kind) c[kFoldBadKind] = 3, c[kFoldBadKind1] = ~41ull;
+      if (len) c[kFoldBadLen] = 2, c[kFoldBadLen1] = ~0ull;  // chunk 0: ~0 is not "none"
+      return c;
+    };
+    FoldVerdict v = fold_counts_verdict(ctr_of(10, 3, false, false, false).data(), n, L);
+    REQUIRE(v.why == FoldVerdict::ok && v.k == 10 && v.b == 3);
+    v = fold_counts_verdict(ctr_of(10, 3, true, false, false).data(), n, L);
+    REQUIRE(v.why == FoldVerdict::bad_layer && v.which == 5);
+    v = fold_counts_verdict(ctr_of(10, 3, false, true, false).data(), n, L);
+    REQUIRE(v.why == FoldVerdict::bad_kind && v.which == 41 && v.count == 3);
+    v = fold_counts_verdict(ctr_of(10, 3, false, false, true).data(), n, L);
+    REQUIRE(v.why == FoldVerdict::bad_len && v.which == 0 && v.count == 2 && v.k == 10 && v.b == 3);
+    // pairs (and an insane count under each refusal): the earlier one is named
+    REQUIRE(fold_counts_verdict(ctr_of(10, 3, true, true, false).data(), n, L).why == FoldVerdict::bad_layer);
+    REQUIRE(fold_counts_verdict(ctr_of(10, 3, true, false, true).data(), n, L).why == FoldVerdict::bad_layer);
+    REQUIRE(fold_counts_verdict(ctr_of(10, 3, false, true, true).data(), n, L).why == FoldVerdict::bad_kind);
+    REQUIRE(fold_counts_verdict(ctr_of(n + 1, 3, true, false, false).data(), n, L).why == FoldVerdict::bad_layer);
+    REQUIRE(fold_counts_verdict(ctr_of(n + 1, 3, false, true, false).data(), n, L).why == FoldVerdict::bad_kind);
+    REQUIRE(fold_counts_verdict(ctr_of(n + 1, 3, false, false, true).data(), n, L).why == FoldVerdict::bad_len);
+    // the sanity bounds at equality and one past it: k <= n, b <= L, b <= k
+    REQUIRE(fold_counts_verdict(ctr_of(n, L, false, false, false).data(), n, L).why == FoldVerdict::ok);
+    v = fold_counts_verdict(ctr_of(n + 1, L, false, false, false).data(), n, L);
+    REQUIRE(v.why == FoldVerdict::insane && v.k == n + 1 && v.b == L);
+    REQUIRE(fold_counts_verdict(ctr_of(n, L + 1, false, false, false).data(), n, L).why == FoldVerdict::insane);
+    REQUIRE(fold_counts_verdict(ctr_of(4, 4, false, false, false).data(), n, L).why == FoldVerdict::ok);
+    REQUIRE(fold_counts_verdict(ctr_of(4, 5, false, false, false).data(), n, L).why == FoldVerdict::insane);
+    REQUIRE(fold_counts_verdict(ctr_of(0, 0, false, false, false).data(), 0, 1).why == FoldVerdict::ok);
+    REQUIRE(fold_counts_verdict(ctr_of(1, 0, false, false, false).data(), 0, 1).why == FoldVerdict::insane);
+  }
   printf("ok %d\n", checks);
   return 0;
 }

@@ -163,6 +163,20 @@ int main() {
       }
     }
   }
+  // ---- the scratch layout: the offsets written out by hand ----
+  for (uint64_t m : {0ull, 1ull, 63ull, 64ull, 65ull, 16383ull, 16384ull, 16385ull})
+    for (uint64_t bw : {1ull, 2ull, 32768ull})        // bitmap words: at least one
+      for (uint64_t rw : {0ull, 1ull, 1000ull}) {     // remap words: one per blob
+        const uint64_t nw = (m + 63) / 64, nt = (nw + 255) / 256;
+        const RetireScratch s = retire_scratch_layout(m, bw, rw);
+        REQUIRE(dict_retire_scan_tiles(m) == nt);
+        REQUIRE(s.words == 0 && s.sums == 8 * nw && s.cnt == 8 * nw + 8 * (nt + 1));
+        REQUIRE(s.bits == 8 * nw + 8 * (nt + 1) + 4 * nw && s.remap == s.bits + 4 * bw);
+        REQUIRE(s.bytes == 8 * nw + 8 * (nt + 1) + 4 * nw + 4 * bw + 4 * rw);
+        REQUIRE(s.words % 8 == 0 && s.sums % 8 == 0 && s.cnt % 4 == 0 && s.bits % 4 == 0 && s.remap % 4 == 0);
+        REQUIRE(s.words + 8 * nw <= s.sums && s.sums + 8 * (nt + 1) <= s.cnt && s.cnt + 4 * nw <= s.bits &&
+                s.bits + 4 * bw <= s.remap && s.remap + 4 * rw <= s.bytes);
+      }
   printf("ok %d\n", checks);
   return 0;
 }

@@ -356,7 +356,7 @@ def _random_layer(rng, total, chunk_size):
 def test_c3_sha256_dict_bootstrap_1m_entries_vs_oracle(oracle, tmp_path, m):
     """BASELINE configs[2] shape at test size: sha256 digester, 1 MiB chunks,
     a chunk dict of >= 1M entries loaded from a sha256 RAFS v6 bootstrap (4M
-    entries = 320 MB of chunk table: the streamed load, csrc/dict.hip
+    entries = 320 MB of chunk table: the streamed load, csrc/dict_load.hip
     dict_stream_v6, four 1M-record pieces; the later duplicates sit in
     other pieces than their first rows), with
     planted layer digests, keys duplicated later in the table (first wins),

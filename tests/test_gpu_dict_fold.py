@@ -570,6 +570,42 @@ def test_extend_device_equals_extend_of_the_same_rows(n):
         eng.device_status()
 
 
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_create_device_with_global_ids_equals_create_of_the_same_rows(n):
+    """create_device with a global id array (the SoA pack kernel's other gid source),
+    with and without the index / offset arrays, against create() of the same rows as
+    80-B records: the same exported rows, and every probe hit the host-path dict's
+    with its entry (a position there) looked up in the id array."""
+    import torch
+    rng = np.random.default_rng(9500 + n)
+    nb = 3
+    with nydus_gpu.Engine(chunk_size=CS) as eng:
+        (dg, us, bl, ix, uo), rows = _base_arrays(rng, n, nb)
+        gid = rng.permutation(n).astype(np.uint32) + 1000
+        d_gid = _dev(gid)
+        q = _dev(np.concatenate([rows["block_id"], rng.integers(0, 256, (5, 32), dtype=np.uint8)]))
+        torch.cuda.synchronize()
+        bare = rows.copy()
+        bare["index"] = 0
+        bare["uncompressed_offset"] = 0
+        for tag, exp, p_ix, p_uo in (("all arrays", rows, ix.data_ptr(), uo.data_ptr()),
+                                     ("no index / uoff arrays", bare, 0, 0)):
+            d = eng.dict_create_device(dg.data_ptr(), us.data_ptr(), bl.data_ptr(), p_ix, n, nb,
+                                       d_uoff=p_uo, d_gid=d_gid.data_ptr())
+            host = eng.dict_create(exp)
+            _same_rows(d.export()[0], exp, f"n={n} {tag}: export vs the rows")
+            _same_rows(d.export()[0], host.export()[0], f"n={n} {tag}: export vs the host path")
+            got, ref = _probe(d, q, n + 5), _probe(host, q, n + 5)
+            hit = ref["entry"] != 0xFFFFFFFF
+            assert hit[:n].all() and not hit[n:].any()
+            want = ref.copy()
+            want["entry"][hit] = gid[ref["entry"][hit]]
+            assert got.tobytes() == want.tobytes(), f"n={n} {tag}: probe hits"
+            d.release()
+            host.release()
+        eng.device_status()
+
+
 def test_extend_device_refusals():
     import torch
     rng = np.random.default_rng(61)
