@@ -418,7 +418,7 @@ int ngpu_dict_retire(ngpu_engine *eng, ngpu_dict *base, const uint32_t *blobs, u
  * is given and the handle has one (ngpu_dict_info.has_blob_table; blob_cap rows
  * of room, too few: NGPU_EINVAL, nothing written).  Plain dicts and replicated
  * node dicts (part 0's rows, the node handle's placements); a partitioned node
- * dict returns NGPU_EUNSUPP. */
+ * dict returns NGPU_EUNSUPP here: ngpu_node_dict_export takes both node modes. */
 int ngpu_dict_export(ngpu_engine *eng, const ngpu_dict *d, void *records, uint64_t cap,
                      uint64_t *n_records, void *blob_table, uint32_t blob_cap, uint32_t *n_blobs);
 typedef struct {
@@ -752,12 +752,51 @@ int ngpu_node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_p
                         const void *blob_table, uint32_t n_blobs, uint32_t flags, ngpu_dict **out);
 /* ngpu_dict_retire for node dicts.  A replicated dict retires every replica
  * with the same result (global id = position) and the node handle's placement
- * rows follow.  A partitioned dict returns NGPU_EUNSUPP: its parts' new global
- * ids are ranks across all parts, which this call does not compute yet.  A
- * plain dict here is NGPU_EINVAL.  *out is NULL on every failure and base stays
- * usable. */
+ * rows follow.  A partitioned dict returns NGPU_EUNSUPP from this call, as it
+ * always has: ngpu_node_dict_retire_parts retires both modes.  A plain dict here
+ * is NGPU_EINVAL.  *out is NULL on every failure and base stays usable. */
 int ngpu_node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
                           uint32_t flags, ngpu_dict **out);
+/* ngpu_dict_retire for node dicts of both modes (additive in ABI 7).  A replicated
+ * dict goes the way of ngpu_node_dict_retire.  For a partitioned dict the contract
+ * is ngpu_dict_retire's, stated on the whole dict: out answers every probe, Pack,
+ * ngpu_node_process_device / _step and export as ngpu_node_dict_create does, in
+ * base's mode and exchange, over base's records without those of the listed blobs.
+ * Records stay in global table order, kept blobs are re-ranked, the kept blob
+ * table rows and the placement rows are kept iff base had them, entry ids (the
+ * global ids the parts' hits carry) are positions among ALL parts' survivors, and
+ * the first entry still wins.  Only the handle's own entries(base) count: rows a
+ * later in-place extend or fold appended to the parts' storages are not seen.
+ * base is only read: probes of it may run meanwhile.
+ *
+ * Every part of out sits on a storage of its own with ngpu_dict_retire's room for
+ * its own survivors (s + s / 2 record slots), the node handle on placement rows
+ * for all of them, so later extends and folds append in place.  n == 0 is a
+ * compacting copy; retiring every blob gives a valid dict of 0 entries.  The
+ * device work runs on streams of the library's own, one per part, which exchange
+ * one keep bit per entry of base between the parts (W x entries / 8 bytes into
+ * every part); all of them are synchronised when the call returns, on every path.
+ *
+ * Rejected before any GPU work, with *out = NULL: a NULL argument, flags != 0,
+ * n && !blobs, an index >= blobs(base), a plain dict, a dict of another node
+ * (NGPU_EINVAL).  Parts whose global ids do not tile [0, entries(base)) -- an id
+ * past the end or held twice -- are NGPU_EINVAL before anything is allocated. */
+int ngpu_node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                                uint32_t flags, ngpu_dict **out);
+/* ngpu_dict_export for node dicts of both modes (additive in ABI 7), with its
+ * contract: *n_records and *n_blobs are always set, records == NULL && cap == 0
+ * only counts, cap < entries(d) or too few blob_cap rows is NGPU_EINVAL with
+ * nothing written.  A replicated dict goes the way of ngpu_dict_export.  For a
+ * partitioned dict every part's rows come back from its device and each becomes
+ * the record at the position of its global id, its compressed fields from the node
+ * handle's placement row there (without placement rows: the defaults
+ * ngpu_dict_export documents).  Every id must be below entries(d) and every
+ * position written exactly once, else NGPU_EINVAL, and what records holds is
+ * unspecified then.  flags must be 0; a plain dict or a dict of another node is
+ * NGPU_EINVAL. */
+int ngpu_node_dict_export(ngpu_node *node, const ngpu_dict *d, void *records, uint64_t cap,
+                          uint64_t *n_records, void *blob_table, uint32_t blob_cap, uint32_t *n_blobs,
+                          uint32_t flags);
 int ngpu_node_dict_create(ngpu_node *node, const void *records, uint64_t n,
                           const void *blob_table, uint32_t n_blobs, uint32_t mode,
                           ngpu_dict **out);

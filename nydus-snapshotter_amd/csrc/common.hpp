@@ -346,6 +346,27 @@ uint64_t node_split_tiles(uint64_t k);
 void launch_node_split(const DictRec *rows, uint64_t k, uint32_t W, uint32_t *cnt, uint64_t *sums,
                        DictRec *out, hipStream_t s);
 
+// node_retire.hip (retire of a partitioned node dict, node.hip; the scratch
+// arrays and the counter block ctr are laid out by node_retire_plan.hpp).
+// Per part: launch_dict_keep_scan's keep words, prefixes and s_o (sums' last
+// word) over its m_o rows, and bit gid of gbits ((m + 63) / 64 words, zeroed on s
+// by the caller) for every kept row; a gid >= m sets nothing and is counted.
+void launch_node_keep_scan(const DictRec *rec, uint64_t m_o, const uint32_t *bitmap, uint32_t n_blobs,
+                           uint64_t m, uint64_t *words, uint32_t *cnt, uint64_t *sums, uint64_t *gbits,
+                           uint64_t *ctr, hipStream_t s);
+// gather: the W parts' bitmaps, part p's (m + 63) / 64 words at p * that many.
+// Their OR to gwords, its popcounts scanned in gcnt (gsums: the scan's sums, S
+// last), words set by two parts counted; then *s_local and S into ctr.
+void launch_node_keep_merge(const uint64_t *gather, uint32_t W, uint64_t m, uint64_t *gwords,
+                            uint32_t *gcnt, uint64_t *gsums, const uint64_t *s_local, uint64_t *ctr,
+                            hipStream_t s);
+// launch_dict_compact over a part's rows, with gid = the rank of the row's old
+// gid among the set bits of gwords (gprefix: their scanned counts).
+void launch_node_dict_compact(const DictRec *rec, uint64_t m_o, const uint64_t *words,
+                              const uint32_t *prefix, const uint64_t *gwords, const uint32_t *gprefix,
+                              uint64_t m, const uint32_t *remap, uint32_t n_blobs, DictRec *out,
+                              uint64_t s_o, hipStream_t s);
+
 // Device workspace, grown on demand and owned by the engine.
 struct Workspace {
   uint64_t *groups = nullptr;     // n+1: leaf groups per chunk -> exclusive scan

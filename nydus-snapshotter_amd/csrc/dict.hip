@@ -80,8 +80,8 @@ ngpu_dict *default_dict(ngpu_engine *e) {  // e->mu held
 // A storage of rec_cap record slots and table_cap hash slots (place: with host
 // placement rows), none of them reserved yet.  The rows are malloc'ed, not
 // zeroed: the pages past the last row written are never touched.
-static int storage_alloc(ngpu_engine *e, uint64_t rec_cap, uint64_t table_cap, bool place,
-                         DictStorage **out) {
+int storage_alloc(ngpu_engine *e, uint64_t rec_cap, uint64_t table_cap, bool place,
+                  DictStorage **out) {
   DictStorage *st = new DictStorage();
   st->device = e->device;
   st->rec_cap = rec_cap;
@@ -109,7 +109,7 @@ static int storage_alloc(ngpu_engine *e, uint64_t rec_cap, uint64_t table_cap, b
 }
 
 // Point d at entries [0, m) of the storage it holds.
-static void dict_bind(ngpu_dict *d, uint64_t m, uint32_t n_blobs) {
+void dict_bind(ngpu_dict *d, uint64_t m, uint32_t n_blobs) {
   DictDevice &v = d->dev;
   v.rec = d->st->rec;
   v.table = d->st->table;
@@ -719,6 +719,24 @@ int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector
   return 0;
 }
 
+void dict_export_row(const DictRec &r, const DictPlace *row, uint8_t *dst) {
+  RafsV6ChunkInfo x;
+  memset(&x, 0, sizeof x);
+  memcpy(x.block_id, r.digest, 32);
+  x.blob_index = r.blob;
+  x.uncompressed_size = r.usize;
+  x.uncompressed_offset = r.uoff;
+  x.index = r.index;
+  if (row) {
+    x.compressed_offset = row->compressed_offset;
+    x.compressed_size = row->compressed_size;
+    x.flags = row->flags;
+  } else {  // as ngpu_dict_load documents: stored uncompressed at offset 0
+    x.compressed_size = r.usize;
+  }
+  memcpy(dst, &x, 80);
+}
+
 // The handle's own rows back as 80-B RAFS v6 chunk-info records: the HBM rows of
 // p (a plain dict or a replica) in pieces of 1M, the placement rows of `rows`.
 static int dict_export_records(ngpu_engine *e, const ngpu_dict *p, const DictPlace *rows,
@@ -736,24 +754,7 @@ static int dict_export_records(ngpu_engine *e, const ngpu_dict *p, const DictPla
             hipSuccess ||
         hipStreamSynchronize(bs.s) != hipSuccess)
       return fail(e, NGPU_EHIP, "dict export: copy of the records failed");
-    for (uint64_t i = 0; i < c; ++i) {
-      const DictRec &r = h[i];
-      RafsV6ChunkInfo x;
-      memset(&x, 0, sizeof x);
-      memcpy(x.block_id, r.digest, 32);
-      x.blob_index = r.blob;
-      x.uncompressed_size = r.usize;
-      x.uncompressed_offset = r.uoff;
-      x.index = r.index;
-      if (rows) {
-        x.compressed_offset = rows[a + i].compressed_offset;
-        x.compressed_size = rows[a + i].compressed_size;
-        x.flags = rows[a + i].flags;
-      } else {  // as ngpu_dict_load documents: stored uncompressed at offset 0
-        x.compressed_size = r.usize;
-      }
-      memcpy(records + 80 * (a + i), &x, 80);
-    }
+    for (uint64_t i = 0; i < c; ++i) dict_export_row(h[i], rows ? rows + a + i : nullptr, records + 80 * (a + i));
   }
   return 0;
 }

@@ -430,6 +430,13 @@ int dict_place_extend(ngpu_engine *e, ngpu_dict *base, const DictPlace *rows, ui
 int fold_lane(ngpu_engine *e, uint64_t bytes);
 // A kept device buffer of at least `bytes`, grown by half again (msg: the refusal).
 int grow_kept(ngpu_engine *e, uint8_t **ptr, uint64_t *cap, uint64_t bytes, const char *msg);
+// A storage of rec_cap record slots and table_cap hash slots (place: with host
+// placement rows), none reserved yet; d pointed at entries [0, m) of the storage it holds.
+int storage_alloc(ngpu_engine *e, uint64_t rec_cap, uint64_t table_cap, bool place, DictStorage **out);
+void dict_bind(ngpu_dict *d, uint64_t m, uint32_t n_blobs);
+// One HBM row as the 80-B RAFS v6 chunk-info record dict export writes; row: its
+// placement row, null: the documented defaults.
+void dict_export_row(const DictRec &r, const DictPlace *row, uint8_t *dst);
 // A storage of `cap` placement rows and nothing else (node dicts' global handles).
 int storage_alloc_place_only(ngpu_engine *e, uint64_t cap, DictStorage **out);
 // The refusals of a fold's counters, of its placement rule and of its blob table's

@@ -34,6 +34,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <chrono>
 
 #include <rccl/rccl.h>
 
@@ -41,6 +42,7 @@
 #include "dict_retire_plan.hpp"
 #include "engine_internal.hpp"
 #include "node_fold_plan.hpp"
+#include "node_retire_plan.hpp"
 
 using namespace ngpu;
 
@@ -203,6 +205,10 @@ int node_dict_hits(ngpu_engine *e, ngpu_dict *d, const uint8_t *digests, uint64_
   if (n > ws.cap_x || !ws.xq) {
     if (ws.xq) (void)hipFree(ws.xq), ws.xq = nullptr;
     if (ws.xhits) (void)hipFree(ws.xhits), ws.xhits = nullptr;
+    // cap_x is the routed exchange's too: its row ids go with the old size, so
+    // that it allocates all three again and never routes n <= cap_x rows into a
+    // shorter xrow
+    if (ws.xrow) (void)hipFree(ws.xrow), ws.xrow = nullptr;
     const uint64_t c = next_pow2(n < 1024 ? 1024 : n);
     HIP_TRY(e, hipMalloc((void **)&ws.xq, c * 32));
     HIP_TRY(e, hipMalloc((void **)&ws.xhits, c * sizeof(ngpu_dict_hit)));
@@ -374,8 +380,8 @@ int node_dict_extend(ngpu_node *node, ngpu_dict *base, const uint8_t *recs, uint
 
 // base without the records of the listed blobs (dict.hip "dict retire"): every
 // replica retired alike, the global placement rows compacted by part 0's keep
-// words.  Partitioned dicts: a part's new global ids are ranks over all parts'
-// keep bits, which no kernel computes yet.
+// words.  Partitioned dicts are refused here (the answer ngpu_node_dict_retire
+// has always given): node_dict_retire_parts below retires them.
 int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
                      ngpu_dict **out) {
   ngpu_engine *e0 = node->eng[0];
@@ -425,6 +431,324 @@ int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, ui
   }
   d->blob_table = dict_retire_blob_table(base->blob_table, plan.remap);
   *out = d;
+  return 0;
+}
+
+// ---- node dict retire across parts ---------------------------------------------
+// ngpu_node_dict_retire_parts: the retire of a partitioned dict.  The parts tile
+// the old global ids [0, m); a part's new global ids are ranks over all parts'
+// keep bits.  Per part o, on a build stream on its device and one scratch
+// allocation (node_retire_plan.hpp):
+//   1. the retire bitmap and the remap go up, the part's bitmap over [0, m) is
+//      zeroed, launch_node_keep_scan gives the local keep words, prefixes and s_o
+//      and sets bit gid of every kept row; an event.  All W parts are enqueued
+//      before anything waits.
+//   2. the part's stream waits for every other part's event and copies their
+//      bitmaps in (hipMemcpyPeerAsync; its own device to device);
+//      launch_node_keep_merge ORs them, scans the popcounts and leaves s_o, S and
+//      the three counters in one block, copied to pinned memory.  Part 0 also
+//      brings the global keep words and prefixes back when base keeps placement
+//      rows.  The same work on every part: no lead device, no broadcast, no
+//      second exchange.  The call's only mid-way wait follows.
+//   3. the host verdict; every refusal comes before a storage is allocated.
+//   4. launch_node_dict_compact and launch_dict_build on every part's own new
+//      storage, while the host compacts the node handle's placement rows by the
+//      global keep words.
+//   5. the handle, as the replicated path assembles it.
+// Nothing of base's storages is written; every stream is waited for on every path.
+struct RetirePart {
+  std::unique_ptr<BuildStream> bs;
+  hipEvent_t ready = nullptr;  // its bitmap is complete
+  hipEvent_t t[5] = {};        // NGPU_DICT_TRACE=1: keep, gather + merge, compact + build
+  uint8_t *scr = nullptr;
+  NodeRetireScratch lay;
+  uint64_t m_o = 0;
+  DictStorage *dst = nullptr;
+};
+
+int node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                           ngpu_dict **out) {
+  ngpu_engine *e0 = node->eng[0];
+  const uint32_t W = (uint32_t)node->eng.size();
+  if (int rc = node_dict_base_check(node, base, "retire")) return rc;
+  if (base->replicated) return node_dict_retire(node, base, blobs, n, out);
+  const DictRetirePlan plan = dict_retire_plan(base->dev.n_blobs, blobs, n);
+  if (!plan.ok)
+    return fail(e0, NGPU_EINVAL, "node dict retire: blob %u of a dict of %u blobs", plan.bad,
+                base->dev.n_blobs);
+  const uint64_t m = base->dev.m, gnw = (m + 63) / 64;
+  const uint32_t nb0 = base->dev.n_blobs;
+  const DictPlace *rows = base->place();
+  const char *tv = getenv("NGPU_DICT_TRACE");
+  const bool trace = tv && tv[0] == '1';
+  // the trace's host side: milliseconds since the call began at the end of each phase
+  const auto t_begin = std::chrono::steady_clock::now();
+  double t_host[5] = {};
+  auto stamp = [&](int i) {
+    if (trace) t_host[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  };
+  std::vector<RetirePart> pt(W);
+  // the engines' kept pinned counter words (fold_h, under fold_mu in index order as
+  // node_dict_fold takes them): a pinned allocation per call costs milliseconds
+  std::vector<std::unique_lock<std::mutex>> lanes;
+  for (uint32_t o = 0; o < W; ++o) lanes.emplace_back(node->eng[o]->fold_mu);
+  for (uint32_t o = 0; o < W; ++o) {
+    ngpu_engine *e = node->eng[o];
+    DeviceGuard dg(e->device);
+    if (!e->fold_h && hipHostMalloc((void **)&e->fold_h, 512) != hipSuccess) {
+      (void)hipGetLastError();
+      e->fold_h = nullptr;
+      return fail(e0, NGPU_ENOMEM, "node dict retire: pinned counters");
+    }
+  }
+  static_assert(8 * kNodeRetireCtrWords <= 512, "the counters fit the engines' pinned words");
+  std::vector<uint64_t> h_ctr((size_t)W * kNodeRetireCtrWords);
+  DictKeep keep;
+  int rc = 0;
+  auto quiesce = [&] {  // every stream the call used, whatever another one said
+    for (uint32_t o = 0; o < W; ++o) {
+      if (!pt[o].bs || !pt[o].bs->s) continue;
+      DeviceGuard dg(node->dev[o]);
+      if (hipStreamSynchronize(pt[o].bs->s) != hipSuccess && !rc)
+        rc = fail(e0, NGPU_EHIP, "node dict retire: part %u failed on its device", o);
+    }
+  };
+  auto release = [&] {  // after quiesce(): the scratch, the events, storages not handed over
+    for (uint32_t o = 0; o < W; ++o) {
+      RetirePart &p = pt[o];
+      DeviceGuard dg(node->dev[o]);
+      if (p.scr) (void)hipFree(p.scr);
+      if (p.ready) (void)hipEventDestroy(p.ready);
+      for (hipEvent_t ev : p.t)
+        if (ev) (void)hipEventDestroy(ev);
+      storage_unref(p.dst);
+    }
+  };
+  auto mark = [&](RetirePart &p, int i) {
+    if (trace && p.t[i]) (void)hipEventRecord(p.t[i], p.bs->s);
+  };
+
+  // 1. every part's keep words and its bitmap over the global ids
+  for (uint32_t o = 0; o < W && !rc; ++o) {
+    RetirePart &p = pt[o];
+    const ngpu_dict *bp = base->parts[o];
+    DeviceGuard dg(node->dev[o]);
+    p.m_o = bp->dev.m;
+    p.lay = node_retire_scratch_layout(p.m_o, m, W, plan.bitmap.size(), plan.remap.size());
+    p.bs.reset(new BuildStream(node->dev[o]));
+    if (!p.bs->s || hipEventCreateWithFlags(&p.ready, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: no build stream", o);
+      break;
+    }
+    for (int i = 0; trace && i < 5; ++i)
+      if (hipEventCreate(&p.t[i]) != hipSuccess) p.t[i] = nullptr;
+    if (hipMalloc((void **)&p.scr, p.lay.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      p.scr = nullptr;
+      rc = fail(e0, NGPU_ENOMEM, "node dict retire: part %u: scratch allocation failed", o);
+      break;
+    }
+    const hipStream_t s = p.bs->s;
+    uint64_t *d_ctr = (uint64_t *)(p.scr + p.lay.ctr);
+    bool ok = hipMemcpyAsync(p.scr + p.lay.bits, plan.bitmap.data(), 4 * plan.bitmap.size(),
+                             hipMemcpyHostToDevice, s) == hipSuccess &&
+              (plan.remap.empty() || hipMemcpyAsync(p.scr + p.lay.remap, plan.remap.data(),
+                                                    4 * plan.remap.size(), hipMemcpyHostToDevice,
+                                                    s) == hipSuccess) &&
+              hipMemsetAsync(d_ctr, 0, 8 * kNodeRetireCtrWords, s) == hipSuccess &&
+              (!gnw || hipMemsetAsync(p.scr + p.lay.own, 0, 8 * gnw, s) == hipSuccess);
+    if (ok) {
+      mark(p, 0);
+      launch_node_keep_scan(bp->st ? bp->st->rec : nullptr, p.m_o, (const uint32_t *)(p.scr + p.lay.bits),
+                            nb0, m, (uint64_t *)(p.scr + p.lay.words), (uint32_t *)(p.scr + p.lay.cnt),
+                            (uint64_t *)(p.scr + p.lay.sums), (uint64_t *)(p.scr + p.lay.own), d_ctr, s);
+      mark(p, 1);
+      ok = hipGetLastError() == hipSuccess && hipEventRecord(p.ready, s) == hipSuccess;
+    }
+    if (!ok) rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: keep scan failed", o);
+  }
+  // 2. all-gather of the bitmaps, their OR and the global scan, on every part
+  for (uint32_t o = 0; o < W && !rc; ++o) {
+    RetirePart &p = pt[o];
+    DeviceGuard dg(node->dev[o]);
+    const hipStream_t s = p.bs->s;
+    bool ok = true;
+    for (uint32_t q = 0; q < W && ok && gnw; ++q) {
+      uint8_t *to = p.scr + p.lay.gather + 8 * gnw * q;
+      const uint8_t *from = pt[q].scr + pt[q].lay.own;
+      if (q == o)  // written on this very stream
+        ok = hipMemcpyAsync(to, from, 8 * gnw, hipMemcpyDeviceToDevice, s) == hipSuccess;
+      else
+        ok = hipStreamWaitEvent(s, pt[q].ready, 0) == hipSuccess &&
+             hipMemcpyPeerAsync(to, node->dev[o], from, node->dev[q], 8 * gnw, s) == hipSuccess;
+    }
+    if (ok) {
+      uint64_t *d_ctr = (uint64_t *)(p.scr + p.lay.ctr);
+      launch_node_keep_merge((const uint64_t *)(p.scr + p.lay.gather), W, m,
+                             (uint64_t *)(p.scr + p.lay.gwords), (uint32_t *)(p.scr + p.lay.gcnt),
+                             (uint64_t *)(p.scr + p.lay.gsums),
+                             (const uint64_t *)(p.scr + p.lay.sums) + dict_retire_scan_tiles(p.m_o), d_ctr,
+                             s);
+      mark(p, 2);
+      ok = hipGetLastError() == hipSuccess &&
+           hipMemcpyAsync(node->eng[o]->fold_h, d_ctr, 8 * kNodeRetireCtrWords, hipMemcpyDeviceToHost,
+                          s) == hipSuccess;
+    }
+    if (ok && o == 0 && rows && gnw) {
+      keep.words.resize(gnw);
+      keep.prefix.resize(gnw);
+      ok = hipMemcpyAsync(keep.words.data(), p.scr + p.lay.gwords, 8 * gnw, hipMemcpyDeviceToHost, s) ==
+               hipSuccess &&
+           hipMemcpyAsync(keep.prefix.data(), p.scr + p.lay.gcnt, 4 * gnw, hipMemcpyDeviceToHost, s) ==
+               hipSuccess;
+    }
+    if (!ok) rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: gathering the keep bits failed", o);
+  }
+  stamp(0);
+  quiesce();  // the call's only mid-way wait
+  stamp(1);
+  if (rc) {
+    release();
+    return rc;
+  }
+
+  // 3. the verdict; nothing is allocated before it
+  for (uint32_t o = 0; o < W; ++o)
+    memcpy(&h_ctr[(size_t)o * kNodeRetireCtrWords], node->eng[o]->fold_h, 8 * kNodeRetireCtrWords);
+  const NodeRetireVerdict v = node_retire_verdict(W, h_ctr.data(), m);
+  if (!v.ok()) {
+    rc = fail(e0, NGPU_EINVAL,
+              "node dict retire: the parts do not tile the dict's ids (%s, part %u; %llu survivors of %llu)",
+              v.refusal == kNodeRetireCounter
+                  ? (v.which == kNodeRetireBadGid ? "an id past the dict's entries"
+                     : v.which == kNodeRetireDupBit ? "an id held twice" : "an id held by two parts")
+                  : v.refusal == kNodeRetireSum ? "the parts' survivors do not add up" : "too many survivors",
+              v.bad, (unsigned long long)v.S, (unsigned long long)m);
+    release();
+    return rc;
+  }
+  const NodeRetireCaps caps = node_retire_caps(v);
+  const uint64_t S = v.S;
+
+  // 4. every part's survivors onto a storage of its own, and its table
+  for (uint32_t o = 0; o < W && !rc; ++o) {
+    RetirePart &p = pt[o];
+    const ngpu_dict *bp = base->parts[o];
+    DeviceGuard dg(node->dev[o]);
+    if ((rc = storage_alloc(node->eng[o], caps.rec_cap[o], caps.table_cap[o], false, &p.dst))) {
+      rc = fail(e0, rc, "%s", ngpu_last_error(node->eng[o]));
+      break;
+    }
+    p.dst->used = v.s[o];
+    const hipStream_t s = p.bs->s;
+    mark(p, 3);
+    launch_node_dict_compact(bp->st ? bp->st->rec : nullptr, p.m_o, (const uint64_t *)(p.scr + p.lay.words),
+                             (const uint32_t *)(p.scr + p.lay.cnt), (const uint64_t *)(p.scr + p.lay.gwords),
+                             (const uint32_t *)(p.scr + p.lay.gcnt), m, (const uint32_t *)(p.scr + p.lay.remap),
+                             nb0, p.dst->rec, v.s[o], s);
+    launch_dict_build(p.dst->rec, v.s[o], p.dst->table, p.dst->table_cap, s);
+    mark(p, 4);
+    if (hipGetLastError() != hipSuccess)
+      rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: compaction failed", o);
+  }
+  stamp(2);
+  // the node handle's placement rows, while the devices move the records
+  DictStorage *hst = nullptr;
+  if (!rc && !(rc = storage_alloc_place_only(e0, rows && S ? caps.place_cap : 0, &hst))) {
+    hst->rec_cap = caps.place_cap;
+    hst->used = S;
+    if (rows && S) dict_retire_place(keep, m, rows, hst->place, S);
+  }
+  quiesce();
+  stamp(3);
+  if (rc) {
+    storage_unref(hst);
+    release();
+    return rc;
+  }
+  if (trace)
+    for (uint32_t o = 0; o < W; ++o) {
+      float a = 0, b = 0, c = 0;
+      const RetirePart &p = pt[o];
+      if (p.t[0] && p.t[1] && p.t[2] && p.t[3] && p.t[4] &&
+          hipEventElapsedTime(&a, p.t[0], p.t[1]) == hipSuccess &&
+          hipEventElapsedTime(&b, p.t[1], p.t[2]) == hipSuccess &&
+          hipEventElapsedTime(&c, p.t[3], p.t[4]) == hipSuccess)
+        fprintf(stderr,
+                "ngpu node_dict_retire_parts part=%u m=%llu m_o=%llu s_o=%llu device_us=%.1f keep_scan_us=%.1f "
+                "gather_merge_us=%.1f compact_build_us=%.1f\n",
+                o, (unsigned long long)m, (unsigned long long)p.m_o, (unsigned long long)v.s[o],
+                (a + b + c) * 1000.0, a * 1000.0, b * 1000.0, c * 1000.0);
+      (void)hipGetLastError();
+    }
+
+  // 5. the handle
+  ngpu_dict *d = dict_derive(base);
+  d->dev.m = S;
+  d->dev.n_blobs = plan.n_kept;
+  d->st = hst;
+  d->has_place = rows && S;
+  for (uint32_t o = 0; o < W; ++o) {
+    ngpu_dict *p = dict_derive(base->parts[o]);
+    p->st = pt[o].dst;
+    pt[o].dst = nullptr;
+    dict_bind(p, v.s[o], plan.n_kept);
+    d->parts.push_back(p);
+  }
+  d->blob_table = dict_retire_blob_table(base->blob_table, plan.remap);
+  release();
+  stamp(4);
+  if (trace)
+    fprintf(stderr,
+            "ngpu node_dict_retire_parts host W=%u m=%llu enqueue_ms=%.3f wait_ms=%.3f alloc_launch_ms=%.3f "
+            "place_wait_ms=%.3f release_ms=%.3f\n",
+            W, (unsigned long long)m, t_host[0], t_host[1] - t_host[0], t_host[2] - t_host[1],
+            t_host[3] - t_host[2], t_host[4] - t_host[3]);
+  *out = d;
+  return 0;
+}
+
+// ngpu_node_dict_export of a partitioned dict: every part's HBM rows come back in
+// pieces of 1M and each becomes the record at position gid, with the node
+// handle's placement row gid.  The host checks that the parts tile [0, m): every
+// gid below m, no position written twice, m rows in all.
+int node_dict_export_parts(ngpu_node *node, const ngpu_dict *d, uint8_t *records) {
+  ngpu_engine *e0 = node->eng[0];
+  const uint64_t m = d->dev.m;
+  const DictPlace *rows = d->place();
+  uint64_t total = 0;
+  for (const ngpu_dict *p : d->parts) total += p->dev.m;
+  if (total != m)
+    return fail(e0, NGPU_EINVAL, "node dict export: the parts do not tile the dict's ids (%llu rows, %llu entries)",
+                (unsigned long long)total, (unsigned long long)m);
+  if (!m) return 0;
+  std::vector<uint64_t> seen((m + 63) / 64, 0);
+  std::vector<DictRec> h(std::min<uint64_t>(m, 1u << 20));
+  for (size_t o = 0; o < d->parts.size(); ++o) {
+    const ngpu_dict *p = d->parts[o];
+    const uint64_t m_o = p->dev.m;
+    if (!m_o) continue;
+    DeviceGuard dg(p->device);
+    BuildStream bs(p->device);
+    if (!bs.s) return fail(e0, NGPU_EHIP, "chunk dict: no build stream");
+    for (uint64_t a = 0; a < m_o; a += h.size()) {
+      const uint64_t c = std::min<uint64_t>(h.size(), m_o - a);
+      if (hipMemcpyAsync(h.data(), p->st->rec + a, c * sizeof(DictRec), hipMemcpyDeviceToHost, bs.s) !=
+              hipSuccess ||
+          hipStreamSynchronize(bs.s) != hipSuccess)
+        return fail(e0, NGPU_EHIP, "node dict export: copy of part %zu's records failed", o);
+      for (uint64_t i = 0; i < c; ++i) {
+        const uint64_t g = h[i].gid;
+        if (g >= m || ((seen[g >> 6] >> (g & 63)) & 1))
+          return fail(e0, NGPU_EINVAL,
+                      "node dict export: the parts do not tile the dict's ids (id %llu of part %zu, %llu entries)",
+                      (unsigned long long)g, o, (unsigned long long)m);
+        seen[g >> 6] |= 1ull << (g & 63);
+        dict_export_row(h[i], rows ? rows + g : nullptr, records + 80 * g);
+      }
+    }
+  }
   return 0;
 }
 
@@ -1085,6 +1409,39 @@ int ngpu_node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blob
   if (out) *out = nullptr;
   if (!base || flags || !node || !out || (n && !blobs)) return NGPU_EINVAL;
   return guarded([&] { return node_dict_retire(node, base, blobs, n, out); });
+}
+
+int ngpu_node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
+                                uint32_t flags, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!base || flags || !node || !out || (n && !blobs)) return NGPU_EINVAL;
+  return guarded([&] { return node_dict_retire_parts(node, base, blobs, n, out); });
+}
+
+int ngpu_node_dict_export(ngpu_node *node, const ngpu_dict *d, void *records, uint64_t cap,
+                          uint64_t *n_records, void *blob_table, uint32_t blob_cap, uint32_t *n_blobs,
+                          uint32_t flags) {
+  if (n_records) *n_records = d ? d->dev.m : 0;
+  if (n_blobs) *n_blobs = d ? d->dev.n_blobs : 0;
+  if (!node || !d || !n_records || !n_blobs || flags) return NGPU_EINVAL;
+  return guarded([&]() -> int {
+    ngpu_engine *e0 = node->eng[0];
+    if (int rc = node_dict_base_check(node, d, "export")) return rc;
+    if (d->replicated)
+      return ngpu_dict_export(e0, d, records, cap, n_records, blob_table, blob_cap, n_blobs);
+    const uint64_t m = d->dev.m;
+    if (!records && !cap) return 0;  // a count
+    if (cap < m || (m && !records))
+      return fail(e0, NGPU_EINVAL, "node dict export: room for %llu of %llu records",
+                  (unsigned long long)cap, (unsigned long long)m);
+    const bool table = blob_table && !d->blob_table.empty();
+    if (table && 256ull * blob_cap < d->blob_table.size())
+      return fail(e0, NGPU_EINVAL, "node dict export: room for %u of %llu blob records", blob_cap,
+                  (unsigned long long)(d->blob_table.size() / 256));
+    if (int rc = node_dict_export_parts(node, d, (uint8_t *)records)) return rc;
+    if (table) memcpy(blob_table, d->blob_table.data(), d->blob_table.size());
+    return 0;
+  });
 }
 
 static_assert(sizeof(ngpu_node_fold_part) == 40, "ngpu_node_fold_part is 40 bytes");

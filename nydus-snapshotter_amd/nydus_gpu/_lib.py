@@ -90,7 +90,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # dict fold (additive in ABI 7)
            "ngpu_dict_extend_device", "ngpu_dict_fold",
            # node dict fold (additive in ABI 7)
-           "ngpu_node_dict_fold"]
+           "ngpu_node_dict_fold",
+           # node dict retire / export across parts (additive in ABI 7)
+           "ngpu_node_dict_retire_parts", "ngpu_node_dict_export"]
 
 # ngpu_dict_place: the compressed placement of one folded record (host rows)
 DICT_PLACE_DTYPE = np.dtype([("compressed_offset", "<u8"), ("compressed_size", "<u4"), ("flags", "<u4")])
@@ -342,6 +344,8 @@ def lib():
     L.ngpu_dict_retire.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_dict_retire.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32)]
+    L.ngpu_node_dict_retire_parts.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
+    L.ngpu_node_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32), u32]
     L.ngpu_dict_extend_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_dict_fold.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_dict_fold.argtypes = [vp, vp, vp, u32, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
@@ -1578,6 +1582,44 @@ class Node:
         h = ctypes.c_void_p()
         self._err(lib().ngpu_node_dict_retire(self._h, base._h, _ptr(idx), len(idx), 0,
                                               ctypes.byref(h)), "node_dict_retire")
+        return ChunkDict(h)
+
+    def dict_export_parts(self, d: ChunkDict):
+        """ngpu_node_dict_export: (records as rafs.CHUNK_INFO_DTYPE in global table
+        order, the 256-B blob records as bytes or None) of a node dict of either
+        mode; a partitioned dict's rows come back from every part."""
+        from . import rafs
+        L = lib()
+        m, nb = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._err(L.ngpu_node_dict_export(self._h, d._h, None, 0, ctypes.byref(m), None, 0, ctypes.byref(nb), 0),
+                  "node_dict_export")
+        recs = np.zeros(m.value, rafs.CHUNK_INFO_DTYPE)
+        table = np.zeros(256 * nb.value, np.uint8) if nb.value and d._has_blob_table() else None
+        room = recs if m.value else np.zeros(1, rafs.CHUNK_INFO_DTYPE)  # (not the counting call)
+        self._err(L.ngpu_node_dict_export(self._h, d._h, _ptr(room.view(np.uint8).reshape(-1)), len(room),
+                                          ctypes.byref(m), _ptr(table), nb.value if table is not None else 0,
+                                          ctypes.byref(nb), 0), "node_dict_export")
+        return recs, (None if table is None else table.tobytes())
+
+    def dict_retire_parts(self, base: ChunkDict, blobs) -> ChunkDict:
+        """ngpu_node_dict_retire_parts: dict_retire for node dicts of either mode
+        (blobs: indices or 64-hex blob ids); a partitioned dict's parts are
+        compacted on their devices and re-numbered across all of them."""
+        from . import rafs
+        want = list(blobs)
+        if any(isinstance(b, (str, bytes)) for b in want):
+            _, table = self.dict_export_parts(base)
+            ids = [] if table is None else [x.decode() for x in np.frombuffer(table, rafs.BLOB_DTYPE)["blob_id"]]
+            for i, b in enumerate(want):
+                if isinstance(b, (str, bytes)):
+                    s = b.decode() if isinstance(b, bytes) else b
+                    if s not in ids:
+                        raise ValueError(f"blob {s} is not in the dict's blob table")
+                    want[i] = ids.index(s)
+        idx = np.asarray([int(b) for b in want], np.uint32)
+        h = ctypes.c_void_p()
+        self._err(lib().ngpu_node_dict_retire_parts(self._h, base._h, _ptr(idx) if len(idx) else None, len(idx),
+                                                    0, ctypes.byref(h)), "node_dict_retire_parts")
         return ChunkDict(h)
 
     def pack(self, dict=None, retain: bool = False) -> "PackWriter":
