@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "engine_internal.hpp"
+#include "sha256_plan.hpp"
 #include "tarstream.hpp"
 
 using namespace ngpu;
@@ -307,14 +308,14 @@ int enqueue_digest(ngpu_engine *e, const uint8_t *d_data, uint64_t len,
     // tuning override: flags bits 11..13 = 1 + SHA-256 variant (0 split,
     // 1 pair, 2 lane, 4/5 pair layouts)
     const uint32_t sv = (e->cfg.flags >> NGPU_FLAG_SHA_MODE_SHIFT) & 7;
-    // mixed lengths unless the data averages >= 15/16 of a full chunk per
-    // chunk and fills every 32-chunk wave (a raw stream cut at chunk_size,
-    // C3); tar layers and batches mix file-sized chunks with full ones
-    const bool mixed = n % 32 != 0 || len < n * (uint64_t)e->cfg.chunk_size / 16 * 15;
-    launch_sha256(d_data, len, d_chunks, n, d_out, ws.stats + kStBadDesc, sv ? (int)sv - 1 : -1,
-                  mixed, s);
-    snprintf(e->cur->path, sizeof e->cur->path, "sha256 variant %d, %llu chunks",
-             sv ? (int)sv - 1 : -1, (unsigned long long)n);
+    // uniform or masked round waves for the pair kernels: sha256_plan.hpp
+    const int variant = sv ? (int)sv - 1 : -1;
+    const bool mixed = sha_mixed(n, len, e->cfg.chunk_size);
+    launch_sha256(d_data, len, d_chunks, n, d_out, ws.stats + kStBadDesc, variant, mixed, s);
+    char kname[16];
+    sha_pick_name(sha_pick(variant, n, mixed), kname, sizeof kname);
+    snprintf(e->cur->path, sizeof e->cur->path, "sha256 %s, %llu chunks", kname,
+             (unsigned long long)n);
     if (tm) {
       HIP_TRY(e, hipEventRecord(ev[2], s));
       HIP_TRY(e, hipEventRecord(ev[3], s));
@@ -487,8 +488,8 @@ int read_stats_enqueue(ngpu_engine *e, hipStream_t s, uint64_t *h) {
 static int stats_error(ngpu_engine *e, uint64_t bad, uint64_t over, uint64_t unh,
                        uint64_t inv_first, const char *path) {
   if (bad)
-    return fail(e, NGPU_EINVAL, "%llu chunk descriptor(s) outside the data buffer",
-                (unsigned long long)bad);
+    return fail(e, NGPU_EINVAL, "%llu chunk descriptor(s) outside the data buffer (digest stage: %s)",
+                (unsigned long long)bad, path && *path ? path : "caller-supplied digests");
   if (over)
     return fail(e, NGPU_EINVAL, "chunk descriptors overlap (%llu leaves, more than the buffer holds)",
                 (unsigned long long)over);

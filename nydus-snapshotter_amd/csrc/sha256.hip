@@ -12,6 +12,7 @@
 // bounds this kernel.
 #include "common.hpp"
 #include "sha256_core.hpp"  // kK, bswap, xor3, sha_block (shared with verity.hip)
+#include "sha256_plan.hpp"  // sha_pick: the kernel and launch shape of a call
 
 namespace ngpu {
 namespace {
@@ -410,47 +411,23 @@ void launch_sha256(const uint8_t *data, uint64_t data_len,
                    const ngpu_chunk *chunks, uint64_t n, ngpu_result *out,
                    uint64_t *err, int variant, bool mixed, hipStream_t s) {
   if (n == 0) return;
-  // Auto (same-box sweep, profiles/r2/sha_variants_lane_r2sl.jsonl, GB/s):
-  //  * <= 16384 chunks (one 64-chunk workgroup per CU): two lanes per chunk,
-  //    each round wave alone on its SIMD; 16384 x 1 MiB: pair 786, lane 385.
-  //  * <= 32768 chunks: two lanes per chunk, four groups per workgroup (one
-  //    workgroup per CU, a round and a schedule wave on each SIMD); 32768 x
-  //    512 KiB: 1343, against 950 for two 2-group workgroups per CU.
-  //  * more: one lane per chunk, every wave doing its own schedule;
-  //    65536 x 256 KiB lane 1512 / pair-4 1342, 262144 x 64 KiB 1657 / split 1190.
-  if (variant < 0) variant = n <= 256ull * 64 ? 1 : n <= 256ull * 128 ? 5 : 2;
-  if (variant == 2) {
-    hipLaunchKernelGGL(sha256_lane, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, data,
-                       data_len, chunks, n, out, err);
-    return;
+  // which kernel, and why: sha256_plan.hpp
+  const ShaPick p = sha_pick(variant, n, mixed);
+  const dim3 grid((unsigned)p.grid), block(p.threads);
+#define NGPU_SHA_LAUNCH(kernel) \
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, data, data_len, chunks, n, out, err)
+  switch (p.kernel) {
+    case ShaKernel::Split: NGPU_SHA_LAUNCH(sha256_split); break;
+    case ShaKernel::Lane: NGPU_SHA_LAUNCH(sha256_lane); break;
+    case ShaKernel::Pair:
+      if (p.R == 1 && p.uniform) NGPU_SHA_LAUNCH((sha256_pair<1, true>));
+      else if (p.R == 1) NGPU_SHA_LAUNCH((sha256_pair<1, false>));
+      else if (p.R == 4) NGPU_SHA_LAUNCH((sha256_pair<4, false>));
+      else if (p.uniform) NGPU_SHA_LAUNCH((sha256_pair<2, true>));
+      else NGPU_SHA_LAUNCH((sha256_pair<2, false>));
+      break;
   }
-  if (variant >= 1) {
-    const dim3 g2((unsigned)((n + 63) / 64)), g1((unsigned)((n + 31) / 32));
-    // wave-uniform round waves unless the chunks are (nearly) all full-size:
-    // a long chain among short neighbours ran 25-45 % slower masked
-    const bool few = mixed;
-    switch (variant) {
-      case 4:  // one group per workgroup
-        if (few)
-          hipLaunchKernelGGL((sha256_pair<1, true>), g1, dim3(128), 0, s, data, data_len, chunks, n, out, err);
-        else
-          hipLaunchKernelGGL((sha256_pair<1, false>), g1, dim3(128), 0, s, data, data_len, chunks, n, out, err);
-        break;
-      case 5:  // four groups per workgroup: a round and a schedule wave share each SIMD
-        hipLaunchKernelGGL((sha256_pair<4, false>), dim3((unsigned)((n + 127) / 128)), dim3(512), 0, s,
-                           data, data_len, chunks, n, out, err);
-        break;
-      default:
-        if (few)
-          hipLaunchKernelGGL((sha256_pair<2, true>), g2, dim3(256), 0, s, data, data_len, chunks, n, out, err);
-        else
-          hipLaunchKernelGGL((sha256_pair<2, false>), g2, dim3(256), 0, s, data, data_len, chunks, n, out, err);
-    }
-    return;
-  }
-  const uint64_t blocks = (n + 63) / 64;
-  hipLaunchKernelGGL(sha256_split, dim3((unsigned)blocks), dim3(128), 0, s, data,
-                     data_len, chunks, n, out, err);
+#undef NGPU_SHA_LAUNCH
 }
 
 }  // namespace ngpu

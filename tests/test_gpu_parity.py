@@ -17,7 +17,7 @@ import layers
 pytestmark = pytest.mark.gpu
 
 LANES = [1, 2, 4, 8, 16]
-# SHA-256 kernels, forced through ngpu_config.flags bits 11..12 (1 + variant):
+# SHA-256 kernels, forced through ngpu_config.flags bits 11..13 (1 + variant):
 # 0 = auto, one lane per chunk ("split": schedule/round waves; "lane": one wave
 # does both), two lanes per chunk ("pair").
 # "pair" runs two chunk groups per workgroup; 5 forces one group, 6 four groups.
@@ -254,8 +254,10 @@ def test_quad_groups_every_ragged_shape(engines, oracle):
 def test_sha256_ragged_wave(engines, oracle, fl):
     """Chunks of very different block counts in one wave (lanes finish at
     different blocks), lengths around the 55/56/64-byte padding edges, odd
-    offsets (byte-load path), a count that is not a multiple of 32/64, and a
-    bad descriptor in the middle of a wave."""
+    offsets (byte-load path), a count that is not a multiple of 32/64.  The
+    bad descriptor at the end is refused by the host check of process_host
+    before anything is launched; the kernels' own bad-descriptor branches are
+    run by test_gpu_sha_matrix.py."""
     rng = np.random.default_rng(21)
     lens = [1, 55, 56, 63, 64, 65, 119, 120, 128, 4096, 70000, 1 << 20, 3, 200000]
     lens += [int(x) for x in rng.integers(1, 300000, 83)]
