@@ -936,6 +936,76 @@ const char *ngpu_host_error(void);
 /* A ready-made ngpu_write_fn: ctx is a file descriptor ((void *)(intptr_t)fd). */
 int ngpu_write_fd(void *ctx, const void *buf, uint64_t len);
 
+/* ---- dict save: a dict handle written out as a RAFS v6 dict bootstrap (additive
+ * in ABI 7) ----
+ * The handle's records and blob rows go to `w` as the chunk-table-only RAFS v6
+ * bootstrap that ngpu_dict_open, ngpu_dict_extend_bootstrap, ngpu_merge* and
+ * inspect read: bytes [0, 4096) are zero but for the super block magic at 1024
+ * and, at 1152, flags (u64: 0x4 blake3, 0x8 sha256, the handle's digester),
+ * blob_table_offset (u64: 4096, or 0 without blob rows), blob_table_size (u32:
+ * 256 x b), chunk_size (u32), chunk_table_offset (u64: 4096 + 256 x b rounded up
+ * to 4096), chunk_table_size (u64: 80 x k), prefetch offset and size (0).  The
+ * handle's 256-B blob rows follow at 4096 as it holds them, zero padded to the
+ * chunk table; then the k records ngpu_dict_export returns for entries
+ * [first_entry, entries), with blob_index - first_blob.
+ *
+ * The records are made on the device, a window at a time: the window's placement
+ * rows go up (a dict that keeps them), one kernel writes the 80-B records, one
+ * copy brings them into pinned memory and `w` gets them as they are, from the
+ * calling thread, in file order, while the next window is on its way.  Host
+ * memory is two windows (window_records records each; 0: what one staging slot of
+ * the engine holds), whatever the dict's size.  The engine lock is not held; the
+ * call reads only the handle's own rows, so probes and in-place extends of the
+ * same storage may run meanwhile, and so may another save.
+ *
+ * Range save: first_entry = entries(h0) and first_blob = blobs(h0) of a handle h0
+ * that d descends from by extends and folds write only what came after h0, shaped
+ * as ngpu_dict_extend_bootstrap takes it: open(file(h0)) extended by that file
+ * exports what d exports.
+ *
+ * Refused before `w` is called, with *info zeroed (NGPU_EINVAL unless said):
+ * a NULL dict, engine / node or writer; unknown flags or a non-zero reserved word;
+ * first_entry > entries(d) or first_blob > blobs(d); a record in the range whose
+ * blob index is below first_blob (d does not descend from h0 by extends, e.g.
+ * after a retire; one launch over the range finds it, only when first_blob > 0;
+ * the message names the first such entry); a handle that holds records and a blob
+ * count but no blob table, unless NGPU_DICT_SAVE_NO_BLOB_TABLE is set: the file
+ * then carries no blob table and reopening it counts max(blob_index) + 1 blobs,
+ * which is less than blobs(d) when d's last blobs hold no record.  ngpu_dict_save
+ * takes plain dicts and replicated node dicts (part 0's rows); for a partitioned
+ * node dict it returns NGPU_EUNSUPP: ngpu_node_dict_save takes both node modes (a
+ * plain dict there is NGPU_EINVAL).  Two windows the engine's pool cannot give
+ * are NGPU_ENOMEM.  A writer that fails gives NGPU_EIO: the stream is drained,
+ * both windows go back to the pool and the engine's counters read as before.
+ *
+ * A partitioned node dict: every part's rows lie in ascending global id order.
+ * Per window [a, b) each part's slice (found by one lower-bound launch per part
+ * for all the cuts) is copied to node device 0 and a scatter form of the kernel
+ * writes row g to slot g - a.  Rows outside [a, b), a slot written twice or slices
+ * that do not add up to b - a are NGPU_EINVAL ("the parts do not tile the dict's
+ * ids"), possibly after earlier windows were written. */
+#define NGPU_DICT_SAVE_NO_BLOB_TABLE 0x1u
+typedef struct {
+  uint64_t first_entry;     /* 0, or entries() of an ancestor handle that was saved before */
+  uint32_t first_blob;      /* 0, or that handle's blob count */
+  uint32_t flags;
+  uint64_t window_records;  /* records per window; 0: the library's default */
+  uint64_t reserved[2];     /* must be 0 */
+} ngpu_dict_save_options;   /* 40 bytes */
+typedef struct {
+  uint64_t entries, blobs;  /* records and blob rows written */
+  uint64_t bytes;           /* the whole file */
+  uint64_t blob_table_offset, blob_table_size, chunk_table_offset, chunk_table_size;
+  uint64_t windows;
+} ngpu_dict_save_info;      /* 64 bytes */
+/* The layout of a file of `entries` records and `blobs` blob rows (windows = 0);
+ * host only, no engine.  NGPU_EINVAL past ngpu_dict_create's limits. */
+int ngpu_dict_save_layout(uint64_t entries, uint32_t blobs, ngpu_dict_save_info *out);
+int ngpu_dict_save(ngpu_engine *eng, const ngpu_dict *d, const ngpu_dict_save_options *opt /* NULL: zeros */,
+                   ngpu_write_fn w, void *ctx, ngpu_dict_save_info *info /* may be NULL */);
+int ngpu_node_dict_save(ngpu_node *node, const ngpu_dict *d, const ngpu_dict_save_options *opt,
+                        ngpu_write_fn w, void *ctx, ngpu_dict_save_info *info);
+
 /* Host: write the stream of one packed layer whose bytes are in host memory
  * (chunks/results/stats as returned by ngpu_pack_tar).  `data` must be the
  * layer tar the chunks were cut from: its entries are the bootstrap's inode

@@ -437,6 +437,11 @@ void dict_bind(ngpu_dict *d, uint64_t m, uint32_t n_blobs);
 // One HBM row as the 80-B RAFS v6 chunk-info record dict export writes; row: its
 // placement row, null: the documented defaults.
 void dict_export_row(const DictRec &r, const DictPlace *row, uint8_t *dst);
+// Dict save (dict_save.hip): the body of ngpu_dict_save and, with node_call, of
+// ngpu_node_dict_save on the node's first engine (the only one that takes a
+// partitioned dict).  opt: null = zeros; info: may be null.
+int dict_save_run(ngpu_engine *e, const ngpu_dict *d, const ngpu_dict_save_options *opt, bool node_call,
+                  ngpu_write_fn w, void *ctx, ngpu_dict_save_info *info);
 // A storage of `cap` placement rows and nothing else (node dicts' global handles).
 int storage_alloc_place_only(ngpu_engine *e, uint64_t cap, DictStorage **out);
 // The refusals of a fold's counters, of its placement rule and of its blob table's

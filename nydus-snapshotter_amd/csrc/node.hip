@@ -1444,6 +1444,18 @@ int ngpu_node_dict_export(ngpu_node *node, const ngpu_dict *d, void *records, ui
   });
 }
 
+int ngpu_node_dict_save(ngpu_node *node, const ngpu_dict *d, const ngpu_dict_save_options *opt,
+                        ngpu_write_fn w, void *ctx, ngpu_dict_save_info *info) {
+  if (info) memset(info, 0, sizeof *info);
+  if (!node || !d || !w) return NGPU_EINVAL;
+  const int rc = guarded([&]() -> int {
+    if (int rc = node_dict_base_check(node, d, "save")) return rc;
+    return dict_save_run(node->eng[0], d, opt, true, w, ctx, info);
+  });
+  if (rc == NGPU_ENOMEM) fail(node->eng[0], rc, "node dict save: out of memory");
+  return rc;
+}
+
 static_assert(sizeof(ngpu_node_fold_part) == 40, "ngpu_node_fold_part is 40 bytes");
 
 int ngpu_node_dict_fold(ngpu_node *node, ngpu_dict *base, const ngpu_node_fold_part *parts,

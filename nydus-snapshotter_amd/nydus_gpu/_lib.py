@@ -92,7 +92,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # node dict fold (additive in ABI 7)
            "ngpu_node_dict_fold",
            # node dict retire / export across parts (additive in ABI 7)
-           "ngpu_node_dict_retire_parts", "ngpu_node_dict_export"]
+           "ngpu_node_dict_retire_parts", "ngpu_node_dict_export",
+           # dict save (additive in ABI 7)
+           "ngpu_dict_save_layout", "ngpu_dict_save", "ngpu_node_dict_save"]
 
 # ngpu_dict_place: the compressed placement of one folded record (host rows)
 DICT_PLACE_DTYPE = np.dtype([("compressed_offset", "<u8"), ("compressed_size", "<u4"), ("flags", "<u4")])
@@ -103,6 +105,28 @@ class NgpuDictInfo(ctypes.Structure):
                 ("record_capacity", ctypes.c_uint64), ("table_capacity", ctypes.c_uint64),
                 ("shares_base_storage", ctypes.c_uint32), ("has_blob_table", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32 * 2)]
+
+
+DICT_SAVE_NO_BLOB_TABLE = 0x1
+
+
+class NgpuDictSaveOptions(ctypes.Structure):
+    _fields_ = [("first_entry", ctypes.c_uint64), ("first_blob", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("window_records", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+
+class NgpuDictSaveInfo(ctypes.Structure):
+    _fields_ = [("entries", ctypes.c_uint64), ("blobs", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("blob_table_offset", ctypes.c_uint64), ("blob_table_size", ctypes.c_uint64),
+                ("chunk_table_offset", ctypes.c_uint64), ("chunk_table_size", ctypes.c_uint64),
+                ("windows", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert ctypes.sizeof(NgpuDictSaveOptions) == 40 and ctypes.sizeof(NgpuDictSaveInfo) == 64
 
 
 LAYER_STATS_DTYPE = np.dtype([("chunks", "<u8"), ("new_chunks", "<u8"), ("intra_chunks", "<u8"),
@@ -346,6 +370,11 @@ def lib():
     L.ngpu_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32)]
     L.ngpu_node_dict_retire_parts.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32), u32]
+    L.ngpu_dict_save_layout.argtypes = [u64, u32, ctypes.POINTER(NgpuDictSaveInfo)]
+    L.ngpu_dict_save.argtypes = [vp, vp, ctypes.POINTER(NgpuDictSaveOptions), WRITE_FN, vp,
+                                 ctypes.POINTER(NgpuDictSaveInfo)]
+    L.ngpu_node_dict_save.argtypes = [vp, vp, ctypes.POINTER(NgpuDictSaveOptions), WRITE_FN, vp,
+                                      ctypes.POINTER(NgpuDictSaveInfo)]
     L.ngpu_dict_extend_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_dict_fold.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_dict_fold.argtypes = [vp, vp, vp, u32, vp, u64, vp, u32, u32, ctypes.POINTER(vp)]
@@ -722,6 +751,37 @@ def merge(bootstraps, layer_digests, dict_bootstrap: bytes = None, parent_bootst
 DEFAULT_DICT = object()  # "the engine's default dict" (the calls without a dict argument)
 
 
+def dict_save_layout(entries: int, blobs: int) -> dict:
+    """ngpu_dict_save_layout: where the blob table and the chunk table of a saved
+    dict of `entries` records and `blobs` blob rows lie, and the file's size (no GPU)."""
+    x = NgpuDictSaveInfo()
+    _host_check(lib().ngpu_dict_save_layout(entries, blobs, ctypes.byref(x)), "dict_save_layout")
+    return x.as_dict()
+
+
+def _dict_save(call, check, dest, first_entry, first_blob, window_records, no_blob_table):
+    """What ChunkDict.save and Node.dict_save share: options, the sink (a path is
+    written through ngpu_write_fd), the call and its info."""
+    opt = NgpuDictSaveOptions(first_entry=first_entry, first_blob=first_blob,
+                              flags=DICT_SAVE_NO_BLOB_TABLE if no_blob_table else 0,
+                              window_records=window_records)
+    info = NgpuDictSaveInfo()
+    fd = None
+    if isinstance(dest, (str, bytes, os.PathLike)):
+        fd = os.open(dest, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+        sink = _Sink(FdWriter(fd))
+    else:
+        sink = _Sink(dest)
+    try:
+        rc = call(ctypes.byref(opt), sink.fn, sink.ctx, ctypes.byref(info))
+    finally:
+        if fd is not None:
+            os.close(fd)
+    sink.reraise()
+    check(rc, "dict_save")
+    return info.as_dict()
+
+
 class ChunkDict:
     """A chunk dict handle (ngpu_dict*): the HBM-resident HashChunkDict of one
     ChunkDictPath (or of arrays), reference counted.  A pack opened with it
@@ -790,6 +850,19 @@ class ChunkDict:
                                     ctypes.byref(m), _ptr(table), nb.value if table is not None else 0,
                                     ctypes.byref(nb)), "dict_export")
         return recs, (None if table is None else table.tobytes())
+
+    def save(self, dest, *, first_entry: int = 0, first_blob: int = 0, window_records: int = 0,
+             no_blob_table: bool = False, engine=None) -> dict:
+        """ngpu_dict_save: the handle written to `dest` (a path, or an object with
+        write()) as the RAFS v6 dict bootstrap rafs.write_v6_bootstrap gives for
+        its export, made on the GPU a window at a time.  first_entry / first_blob:
+        entries and blobs of an ancestor handle, to write only what came after it.
+        -> {entries, blobs, bytes, blob_table_offset, blob_table_size,
+        chunk_table_offset, chunk_table_size, windows}.  A partitioned node dict
+        goes through Node.dict_save."""
+        e = engine if engine is not None else self._engine()
+        return _dict_save(lambda *a: lib().ngpu_dict_save(e._h, self._h, *a), e._check, dest,
+                          first_entry, first_blob, window_records, no_blob_table)
 
     def _blob_indices(self, blobs, engine=None):
         """ints as they are; 64-hex blob ids through the exported blob table."""
@@ -1573,6 +1646,13 @@ class Node:
     def dict_export(self, d: ChunkDict):
         """ChunkDict.export of a (replicated) node dict."""
         return d.export(self.engines[0])
+
+    def dict_save(self, d: ChunkDict, dest, *, first_entry: int = 0, first_blob: int = 0,
+                  window_records: int = 0, no_blob_table: bool = False) -> dict:
+        """ngpu_node_dict_save: ChunkDict.save for node dicts of either mode; a
+        partitioned dict's rows come from every part, a window at a time."""
+        return _dict_save(lambda *a: lib().ngpu_node_dict_save(self._h, d._h, *a), self._err, dest,
+                          first_entry, first_blob, window_records, no_blob_table)
 
     def dict_retire(self, base: ChunkDict, blobs) -> ChunkDict:
         """ngpu_node_dict_retire: a new node dict of base's entries without those

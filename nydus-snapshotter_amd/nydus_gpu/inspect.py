@@ -20,6 +20,8 @@ usage:
   python -m nydus_gpu.inspect --diff --tree A B  # exit 0 iff the trees match
   python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP]... [--retire BLOBID]... [--chunk-size N] [--digester D]
                                               # re-digest STREAM's chunks on the GPU; exit 1 if any is bad
+  python -m nydus_gpu.inspect --dict BOOTSTRAP [--dict BOOTSTRAP]... [--retire BLOBID]... --save-dict OUT
+                                              # fold the dict bootstraps on the GPU and write the result to OUT
   python -m nydus_gpu.inspect --verity IMAGE [--append]
                                               # the dm-verity tree of a block image; prints its options line
   python -m nydus_gpu.inspect --verity-verify IMAGE --data-blocks N --hash-offset OFF ROOT
@@ -40,6 +42,13 @@ that blob's records from the folded dict (ChunkDict.retire), as a registry's
 garbage collection does: DICT records of a retired blob no longer resolve.
 The digester, chunk size and RAFS version default to the stream's own; the
 report is printed as JSON.
+
+`--save-dict OUT` (ChunkDict.save, ngpu_dict_save) needs a GPU: the dict folded
+from the `--dict` files, after any `--retire`, is written to OUT as a RAFS v6 dict
+bootstrap that `--dict`, ngpu_dict_open and Merge read.  With `--check` the
+report gains "saved_dict": {path, entries, blobs, bytes}; without it the command
+stands alone, takes chunk size and digester from the first `--dict` bootstrap
+unless given, and prints that object.
 
 `--verity` (Engine.verity_file, ngpu_verity_image) needs a GPU: IMAGE is a block
 image (`nydus-image export --block`, a multiple of 512 bytes); the line printed
@@ -62,6 +71,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import struct
 import sys
 
 import numpy as np
@@ -150,11 +160,65 @@ def diff(a: dict, b: dict, fields=("digest", "blob_id", "uncompressed_size")) ->
     return [("-", k) for k in sorted(ka - kb)] + [("+", k) for k in sorted(kb - ka)]
 
 
+def folded_dict(eng, dict_path=None, retire=None):
+    """The dict of the --dict bootstraps on `eng`: the first opened, each further
+    one appended, then the --retire blobs (ids or inner indices) dropped.  None
+    without a --dict; the caller releases it."""
+    paths = [dict_path] if isinstance(dict_path, str) else list(dict_path or [])
+    dct = eng.dict_open(paths[0]) if paths else None
+    try:
+        for p in paths[1:]:
+            grown = dct.extend_bootstrap(p)
+            dct.release()
+            dct = grown
+        if retire:
+            if dct is None:
+                raise ValueError("--retire needs a --dict")
+            kept = dct.retire([int(b) if str(b).isdigit() and len(str(b)) < 64 else b for b in retire])
+            dct.release()
+            dct = kept
+        return dct
+    except BaseException:
+        if dct is not None:
+            dct.release()
+        raise
+
+
+def _save(dct, out: str) -> dict:
+    if dct is None:
+        raise ValueError("--save-dict needs a --dict")
+    info = dct.save(out)
+    return {"path": out, "entries": info["entries"], "blobs": info["blobs"], "bytes": info["bytes"]}
+
+
+def save_dict(out: str, dict_path, chunk_size: int = 0, digester: str = None, retire=None) -> dict:
+    """The dict folded from the --dict bootstraps (after any --retire) written to
+    `out` with ChunkDict.save on GPU 0 -> {path, entries, blobs, bytes}.  Chunk
+    size and digester default to the first bootstrap's."""
+    from ._lib import Engine
+    paths = [dict_path] if isinstance(dict_path, str) else list(dict_path or [])
+    if not paths:
+        raise ValueError("--save-dict needs a --dict")
+    with open(paths[0], "rb") as f:
+        head = f.read(rafs.EXT_OFFSET + 256)
+    if rafs.detect_fs_version(head) != "v6":
+        raise ValueError(f"{paths[0]}: --save-dict takes RAFS v6 dict bootstraps")
+    flags, _, _, cs = struct.unpack_from("<QQII", head, rafs.EXT_OFFSET)
+    with Engine(device=0, digester=digester or ("sha256" if flags & 0x8 else "blake3"),
+                chunk_size=chunk_size or cs, fs_version=6) as eng:
+        dct = folded_dict(eng, paths, retire)
+        try:
+            return _save(dct, out)
+        finally:
+            dct.release()
+
+
 def check(path: str, dict_path=None, chunk_size: int = 0, digester: str = None,
-          max_bad: int = 64, retire=None) -> dict:
+          max_bad: int = 64, retire=None, save_dict: str = None) -> dict:
     """Engine.check of the stream in `path` on GPU 0 (the report dict).
     dict_path: a chunk-dict bootstrap, or a list of them folded into one dict;
-    retire: blob ids (or inner indices) whose records leave the folded dict first."""
+    retire: blob ids (or inner indices) whose records leave the folded dict first;
+    save_dict: write that dict there (ChunkDict.save), reported as "saved_dict"."""
     from ._lib import Engine
     data = np.fromfile(path, np.uint8)
     boot = bootstrap_bytes(data)
@@ -167,20 +231,13 @@ def check(path: str, dict_path=None, chunk_size: int = 0, digester: str = None,
         flags, cs = int(d["flags"]), int(d["chunk_size"])
     with Engine(device=0, digester=digester or ("sha256" if flags & 0x8 else "blake3"),
                 chunk_size=chunk_size or cs, fs_version=6 if v6 else 5) as eng:
-        paths = [dict_path] if isinstance(dict_path, str) else list(dict_path or [])
-        dct = eng.dict_open(paths[0]) if paths else None
+        dct = folded_dict(eng, dict_path, retire)
         try:
-            for p in paths[1:]:
-                grown = dct.extend_bootstrap(p)
-                dct.release()
-                dct = grown
-            if retire:
-                if dct is None:
-                    raise ValueError("--retire needs a --dict")
-                kept = dct.retire([int(b) if str(b).isdigit() and len(str(b)) < 64 else b for b in retire])
-                dct.release()
-                dct = kept
-            return eng.check(data, dict=dct, max_bad=max_bad)
+            saved = _save(dct, save_dict) if save_dict else None
+            rep = eng.check(data, dict=dct, max_bad=max_bad)
+            if saved is not None:
+                rep["saved_dict"] = saved
+            return rep
         finally:
             if dct is not None:
                 dct.release()
@@ -252,6 +309,10 @@ def main(argv=None) -> int:
                     help="--check: chunk-dict bootstrap for DICT records (repeat to fold several into one dict)")
     ap.add_argument("--retire", metavar="BLOBID", action="append",
                     help="--check: drop this blob's records from the folded dict first (repeatable)")
+    ap.add_argument("--save-dict", metavar="OUT",
+                    help="write the dict folded from the --dict files (after any --retire) to OUT as a "
+                         "RAFS v6 dict bootstrap; with --check the report names it, alone it prints "
+                         "{path, entries, blobs, bytes}")
     ap.add_argument("--chunk-size", type=lambda x: int(x, 0), default=0, help="--check: engine chunk size")
     ap.add_argument("--digester", choices=("blake3", "sha256"), help="--check: engine digester")
     ap.add_argument("--verity", metavar="IMAGE", help="dm-verity tree of a block image on the GPU")
@@ -272,13 +333,27 @@ def main(argv=None) -> int:
         except ImportError:
             pass
         try:
-            rep = check(args.check, args.dict, args.chunk_size, args.digester, retire=args.retire)
-        except (NgpuError, ValueError) as e:
+            rep = check(args.check, args.dict, args.chunk_size, args.digester, retire=args.retire,
+                        save_dict=args.save_dict)
+        except (NgpuError, ValueError, OSError) as e:
             print(f"check: {e}", file=sys.stderr)
             return 2
         json.dump(rep, sys.stdout, indent=1)
         print()
         return 1 if rep["bad"] else 0
+    if args.save_dict:
+        try:
+            import torch  # noqa: F401  (one HIP runtime per process: before the library)
+        except ImportError:
+            pass
+        try:
+            rep = save_dict(args.save_dict, args.dict, args.chunk_size, args.digester, retire=args.retire)
+        except (NgpuError, ValueError, OSError) as e:
+            print(f"save-dict: {e}", file=sys.stderr)
+            return 2
+        json.dump(rep, sys.stdout, indent=1)
+        print()
+        return 0
     if args.verity_scan:
         try:
             import torch  # noqa: F401  (one HIP runtime per process: before the library)
