@@ -406,6 +406,73 @@ int ngpu_dict_fold(ngpu_engine *eng, ngpu_dict *base, const ngpu_result *d_resul
  * (NGPU_EINVAL: ngpu_node_dict_retire).  On failure base is untouched. */
 int ngpu_dict_retire(ngpu_engine *eng, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
                      uint32_t flags, ngpu_dict **out);
+/* ---- dict distill: one row per digest, kept by how many rows hold it ----
+ * (additive in ABI 7).  A probe stops at the first row of a digest, so every
+ * later row with the same 32 digest bytes can never answer: it only costs HBM, a
+ * placement row, and time in every save and open.  refs(d) is the number of rows
+ * of base[0, entries(base)) whose 32 digest bytes are d (uncompressed_size takes
+ * no part: this is the table's own view); the winner of d is its first row.
+ *
+ * out equals, for every probe, Pack, Check, stats field, export and save,
+ * ngpu_dict_create over:
+ *   the winners of base, in table order, whose refs >= max(min_refs, 1), each
+ *   unchanged but for its blob index;
+ *   the blob rows as the flags say (below).
+ * Entry ids are positions among the survivors.  min_refs <= 1 is the pure
+ * clean-up: every digest answers as in base (same blob id, chunk index,
+ * uncompressed offset, size and placement); only the entry ids and the inner blob
+ * indices are renumbered.  A larger min_refs keeps the chunks that recur (a row
+ * per layer that referenced the chunk: what nydus's `chunkdict generate` selects
+ * by) and lets go of the rest; above every count it gives a valid dict of 0
+ * entries and 0 blobs, which dedups nothing and can be extended.  out keeps
+ * compressed placements iff base did.
+ *
+ * Blobs.  By default a blob with no surviving row leaves, one that never had a row
+ * included, and the rest are re-ranked in order, exactly as ngpu_dict_retire does;
+ * a base with only a blob count gives out only the new count.
+ * NGPU_DICT_DISTILL_KEEP_BLOBS: blob indices and the blob table stay as they are.
+ * NGPU_DICT_DISTILL_MERGE_BLOB_IDS: every blob whose 256-B row starts with the
+ * same 64 id bytes as an earlier blob's is mapped to the earliest one, whose row
+ * is the one kept; it is live if any of the merged blobs has a survivor.  Refs
+ * still count rows.  It needs a blob table.  Rows whose blob is >= blobs(base)
+ * (ngpu_dict_create_device takes the caller's word) are kept as they are and make
+ * no blob live, as in a retire.
+ *
+ * Only the handle's own entries(base) rows count: rows a later in-place extend
+ * appended to the same storage are not seen.  base is only read: probes, Packs and
+ * in-place extends of base may run meanwhile.  out always sits on a storage of its
+ * own with ngpu_dict_retire's room (s + s / 2 record slots for s survivors), so
+ * the next extends of up to s / 2 records append in place.  The device work (the
+ * counts, the keep bits, their scan, the compaction, the table build) runs on a
+ * stream of the library's own, outside the engine lock, and is complete when the
+ * call returns.  out == NULL only counts: info is filled and no storage is
+ * allocated.  info (may be NULL) is filled on every successful call and zeroed on
+ * every failure.
+ *
+ * What a distill gives up: after a retire, when the winning row of a digest
+ * leaves, the next surviving row with that digest wins.  A distilled dict has no
+ * next row: retiring the blob of a digest's one row forgets the digest, even if
+ * base held it in other blobs too.  Distill trades that fallback for the space.
+ *
+ * Rejected before any GPU work, with *out = NULL (NGPU_EINVAL): base or eng NULL,
+ * flag bits other than the two, both flags together (with KEEP_BLOBS nothing is
+ * merged), MERGE_BLOB_IDS on a dict with records and no blob table, a node dict
+ * (ngpu_node_dict_distill). */
+#define NGPU_DICT_DISTILL_KEEP_BLOBS     0x1u /* leave blob indices and the blob table as they are */
+#define NGPU_DICT_DISTILL_MERGE_BLOB_IDS 0x2u /* blob rows with the same 64-byte blob id become the first of them */
+typedef struct {
+  uint64_t entries_in;    /* entries(base) */
+  uint64_t distinct;      /* digests base holds: rows that win their digest */
+  uint64_t shadowed;      /* entries_in - distinct */
+  uint64_t below_min;     /* distinct digests held by fewer than min_refs rows */
+  uint64_t entries_out;   /* distinct - below_min */
+  uint32_t blobs_in, blobs_out;
+  uint32_t max_refs;      /* the most rows any one digest has (0 for an empty dict) */
+  uint32_t reserved;
+  uint64_t refs_hist[32]; /* [b]: distinct digests with 2^b <= refs < 2^(b+1) */
+} ngpu_dict_distill_info; /* 312 bytes */
+int ngpu_dict_distill(ngpu_engine *eng, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                      ngpu_dict **out /* NULL: count only */, ngpu_dict_distill_info *info /* may be NULL */);
 /* The handle's rows back out of HBM: entries(d) 80-B RAFS v6 chunk-info records in
  * table order and its 256-B blob records, such that ngpu_dict_create over them
  * answers as d does.  block_id, blob_index, uncompressed_size, uncompressed_offset
@@ -783,6 +850,16 @@ int ngpu_node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blob
  * past the end or held twice -- are NGPU_EINVAL before anything is allocated. */
 int ngpu_node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
                                 uint32_t flags, ngpu_dict **out);
+/* ngpu_dict_distill for node dicts (additive in ABI 7), with its contract, flags
+ * and info.  A replicated dict distils every replica alike, with one result and
+ * the node handle's placement rows following: the way ngpu_node_dict_retire goes
+ * (out == NULL counts on the first replica alone).  A partitioned dict is
+ * NGPU_EUNSUPP for now: all rows of a digest live on one part, so the counting is
+ * local, but the global ranks and the union of live blobs need the exchange of
+ * ngpu_node_dict_retire_parts.  A plain dict, or a dict of another node, is
+ * NGPU_EINVAL.  *out is NULL and info zeroed on every failure. */
+int ngpu_node_dict_distill(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                           ngpu_dict **out, ngpu_dict_distill_info *info);
 /* ngpu_dict_export for node dicts of both modes (additive in ABI 7), with its
  * contract: *n_records and *n_blobs are always set, records == NULL && cap == 0
  * only counts, cap < entries(d) or too few blob_cap rows is NGPU_EINVAL with

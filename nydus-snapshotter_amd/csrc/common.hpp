@@ -313,6 +313,20 @@ void launch_dict_compact(const DictRec *rec, uint64_t m, const uint64_t *words,
 // kRetireScanTile); sums: nt + 1 words.
 void launch_retire_scan(uint32_t *cnt, uint64_t nw, uint64_t *sums, hipStream_t s);
 
+// dict_distill.hip (dict distill, dict.hip; the scratch arrays are laid out by
+// dict_distill_plan.hpp).  Launch 1: refs[0, m), zeroed on s by the caller ->
+// the number of rows of rec[0, m) that hold row i's digest when i is the first
+// of them, else 0 (table: the table_cap slots the rows are in).
+void launch_dict_ref_count(const DictRec *rec, uint64_t m, const uint64_t *table, uint64_t table_cap,
+                           uint32_t *refs, hipStream_t s);
+// Launches 2-5: keep word and survivor count per 64 records (a record stays when
+// refs[i] >= max(min_refs, 1)) in launch_dict_keep_scan's format, then the scan;
+// live (one bit per blob, (n_blobs + 31) / 32 words, at least one) and stats
+// (kDistillStatWords u64), both zeroed on s by the caller.
+void launch_distill_keep_scan(const DictRec *rec, uint64_t m, const uint32_t *refs, uint32_t min_refs,
+                              uint32_t n_blobs, uint64_t *words, uint32_t *cnt, uint64_t *sums,
+                              uint32_t *live, uint64_t *stats, hipStream_t s);
+
 // dict_fold.hip (dict fold, dict.hip).  ctr: kFoldCtrWords u64
 // (dict_fold_plan.hpp), zeroed on s by the caller before launch_fold_keep_scan.
 // Launches 1-3: keep word + NEW count per 64 chunks of res[0, n) (a lane per

@@ -1,6 +1,6 @@
 // dict.hip — chunk dicts (PackOption.ChunkDictPath, builder.go:122-124) as
 // reference-counted HBM objects, and their C ABI (include/nydus_gpu.h): storage
-// and handles, create, extend, retire, fold, export and probe.  Loading one from
+// and handles, create, extend, retire, distill, fold, export and probe.  Loading one from
 // a bootstrap file, and the engine's open cache, are dict_load.hip.  A Pack pins
 // the dict it was opened with, so packs against different dicts can be open on
 // one engine at once.
@@ -239,10 +239,10 @@ int storage_alloc_place_only(ngpu_engine *e, uint64_t cap, DictStorage **out) {
 
 namespace {
 
-// NGPU_DICT_TRACE=1: one stderr line per extend, fold or retire with its device
+// NGPU_DICT_TRACE=1: one stderr line per extend, fold, retire or distill with its device
 // time between HIP events (tools/dict_*_bench.py read them); off: no event is made.
 struct DictTrace {
-  hipEvent_t ev[4] = {};
+  hipEvent_t ev[5] = {};
   bool on = false;
   static bool enabled() {
     static const bool t = [] {
@@ -638,6 +638,53 @@ std::vector<uint8_t> dict_retire_blob_table(const std::vector<uint8_t> &table,
   return t;
 }
 
+// What a retire and a distill share once the keep words, their prefixes, the
+// survivor total s and the blob remap lie in HBM (and hk holds the host copy of
+// the words and prefixes when rows are to be moved): the storage of the result,
+// launches 3-4 between events ev and ev + 1 of tr, the placement rows on the host
+// pool meanwhile, and the sync.  *dst: the storage, s of its slots used.
+static int dict_compact_tail(ngpu_engine *e, const char *what, const ngpu_dict *base, hipStream_t bs,
+                             const uint64_t *d_words, const uint32_t *d_cnt, const uint32_t *d_remap,
+                             uint64_t s, const DictPlace *place, const DictKeep &hk, DictTrace &tr,
+                             int ev, DictStorage **dst_out) {
+  const uint64_t m = base->dev.m;
+  DictStorage *dst = nullptr;
+  int rc = 0;
+  if (s > m) rc = fail(e, NGPU_EHIP, "%s: %llu survivors of %llu records", what,
+                       (unsigned long long)s, (unsigned long long)m);
+  if (!rc)
+    rc = storage_alloc(e, dict_retire_rec_cap(s), dict_retire_table_cap(s), place && s, &dst);
+  if (!rc) {
+    dst->used = s;
+    tr.record(ev, bs);
+    launch_dict_compact(base->st ? base->st->rec : nullptr, m, d_words, d_cnt, d_remap,
+                        base->dev.n_blobs, dst->rec, s, bs);
+    launch_dict_build(dst->rec, s, dst->table, dst->table_cap, bs);
+    if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "%s: compaction failed", what);
+    tr.record(ev + 1, bs);
+  }
+  // the placement rows, while the device moves the records
+  if (!rc && place && s) dict_retire_place(hk, m, place, dst->place, s);
+  if (hipStreamSynchronize(bs) != hipSuccess && !rc)
+    rc = fail(e, NGPU_EHIP, "%s: compaction failed", what);
+  if (rc) {
+    storage_unref(dst);
+    return rc;
+  }
+  *dst_out = dst;
+  return 0;
+}
+
+// The handle of a compaction's result: s entries and nb blobs on dst.
+static ngpu_dict *dict_compact_handle(const ngpu_dict *base, DictStorage *dst, uint64_t s, uint32_t nb,
+                                      bool place) {
+  ngpu_dict *d = dict_derive(base);
+  d->st = dst;
+  d->has_place = place && s;
+  dict_bind(d, s, nb);
+  return d;
+}
+
 int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector<uint32_t> &bitmap,
                         const std::vector<uint32_t> &remap, uint32_t nb, const DictPlace *place,
                         DictKeep *keep, ngpu_dict **out) {
@@ -685,38 +732,124 @@ int dict_retire_records(ngpu_engine *e, const ngpu_dict *base, const std::vector
   if (!rc && (hipMemcpyAsync(&s, d_sums + nt, 8, hipMemcpyDeviceToHost, bs.s) != hipSuccess ||
               hipStreamSynchronize(bs.s) != hipSuccess))
     rc = fail(e, NGPU_EHIP, "dict retire: keep scan failed");
-  if (!rc && s > m) rc = fail(e, NGPU_EHIP, "dict retire: %llu survivors of %llu records",
-                              (unsigned long long)s, (unsigned long long)m);
-  if (!rc)
-    rc = storage_alloc(e, dict_retire_rec_cap(s), dict_retire_table_cap(s), place && s, &dst);
   if (!rc) {
-    dst->used = s;
-    tr.record(2, bs.s);
-    launch_dict_compact(base->st ? base->st->rec : nullptr, m, d_words, d_cnt, d_remap, nb0, dst->rec,
-                        s, bs.s);
-    launch_dict_build(dst->rec, s, dst->table, dst->table_cap, bs.s);
-    if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict retire: compaction failed");
-    tr.record(3, bs.s);
+    rc = dict_compact_tail(e, "dict retire", base, bs.s, d_words, d_cnt, d_remap, s, place, hk, tr, 2, &dst);
+  } else if (hipStreamSynchronize(bs.s) != hipSuccess) {
+    (void)hipGetLastError();  // (nothing of the stream still reads the scratch)
   }
-  // the placement rows, while the device moves the records
-  if (!rc && place && s) dict_retire_place(hk, m, place, dst->place, s);
-  if (hipStreamSynchronize(bs.s) != hipSuccess && !rc)
-    rc = fail(e, NGPU_EHIP, "dict retire: compaction failed");
   const double a = rc ? -1.0 : tr.us(0, 1), b = rc ? -1.0 : tr.us(2, 3);
   if (a >= 0 && b >= 0)
     fprintf(stderr, "ngpu dict_retire m=%llu s=%llu device_us=%.1f keep_scan_us=%.1f compact_build_us=%.1f\n",
             (unsigned long long)m, (unsigned long long)s, a + b, a, b);
   (void)hipFree(scr);
-  if (rc) {
-    storage_unref(dst);
-    return rc;
-  }
-  ngpu_dict *d = dict_derive(base);
-  d->st = dst;
-  d->has_place = place && s;
-  dict_bind(d, s, nb);
-  *out = d;
+  if (rc) return rc;
+  *out = dict_compact_handle(base, dst, s, nb, place != nullptr);
   return 0;
+}
+
+// ---- dict distill --------------------------------------------------------------
+// A retire whose keep bits come from the rows themselves: a row stays when it is
+// the first of its digest and at least min_refs rows hold that digest
+// (dict_distill.hip counts them through the table the base already has).  One
+// mid-way copy brings the survivor total, the counters of the info and the
+// blob-live bitmap back; the host turns the bitmap into the blob remap
+// (dict_distill_plan.hpp), uploads it, and the rest is retire's tail.  table: the
+// blob rows MERGE_BLOB_IDS compares (the node handle's for a replica).
+
+int dict_distill_records(ngpu_engine *e, const ngpu_dict *base, const std::vector<uint8_t> &table,
+                         uint32_t min_refs, uint32_t flags, const DictPlace *place, DictKeep *keep,
+                         bool want_out, DictDistilled *res, ngpu_dict **out) {
+  DeviceGuard dg(e->device);
+  const uint64_t m = base->dev.m;
+  const uint32_t nb0 = base->dev.n_blobs;
+  const uint64_t nw = (m + 63) / 64;
+  if (nb0 > kDictMaxBlobs) return fail(e, NGPU_EINVAL, "dict distill: a dict of %u blobs", nb0);
+  BuildStream bs(e->device);
+  if (!bs.s) return fail(e, NGPU_EHIP, "chunk dict: no build stream");
+  const DistillScratch lay = distill_scratch_layout(m, nb0);
+  uint8_t *scr = nullptr;
+  if (hipMalloc((void **)&scr, lay.bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(e, NGPU_ENOMEM, "dict distill: scratch allocation failed");
+  }
+  uint64_t *d_words = (uint64_t *)(scr + lay.words), *d_sums = (uint64_t *)(scr + lay.sums),
+           *d_stats = (uint64_t *)(scr + lay.stats);
+  uint32_t *d_cnt = (uint32_t *)(scr + lay.cnt), *d_live = (uint32_t *)(scr + lay.live),
+           *d_remap = (uint32_t *)(scr + lay.remap), *d_refs = (uint32_t *)(scr + lay.refs);
+  const DictRec *rec = base->st ? base->st->rec : nullptr;
+  // the trace line's device time: launch 1, launches 2-5, and the tail's two
+  DictTrace tr(5);
+  int rc = 0;
+  DictStorage *dst = nullptr;
+  DictKeep own_keep;
+  DictKeep &hk = keep ? *keep : own_keep;
+  std::vector<uint8_t> back(lay.back_bytes);
+  if (hipMemsetAsync(scr + lay.back, 0, lay.back_bytes, bs.s) != hipSuccess ||
+      (m && hipMemsetAsync(d_refs, 0, 4 * m, bs.s) != hipSuccess))
+    rc = fail(e, NGPU_EHIP, "dict distill: clearing the counters failed");
+  if (!rc) {
+    tr.record(0, bs.s);
+    launch_dict_ref_count(rec, m, base->st ? base->st->table : nullptr,
+                          base->st ? base->st->table_cap : 0, d_refs, bs.s);
+    tr.record(1, bs.s);
+    launch_distill_keep_scan(rec, m, d_refs, min_refs, nb0, d_words, d_cnt, d_sums, d_live, d_stats,
+                             bs.s);
+    if (hipGetLastError() != hipSuccess) rc = fail(e, NGPU_EHIP, "dict distill: counting failed");
+    tr.record(2, bs.s);
+  }
+  if (!rc && want_out && (place || keep) && nw) {
+    hk.words.resize(nw);
+    hk.prefix.resize(nw);
+    if (hipMemcpyAsync(hk.words.data(), d_words, 8 * nw, hipMemcpyDeviceToHost, bs.s) != hipSuccess ||
+        hipMemcpyAsync(hk.prefix.data(), d_cnt, 4 * nw, hipMemcpyDeviceToHost, bs.s) != hipSuccess)
+      rc = fail(e, NGPU_EHIP, "dict distill: keep words did not come back");
+  }
+  // the survivor total, the counters and the live blobs: the call's one mid-way copy
+  if (!rc && (hipMemcpyAsync(back.data(), scr + lay.back, lay.back_bytes, hipMemcpyDeviceToHost, bs.s) !=
+                  hipSuccess ||
+              hipStreamSynchronize(bs.s) != hipSuccess))
+    rc = fail(e, NGPU_EHIP, "dict distill: counting failed");
+  uint64_t s = 0;
+  uint64_t stats[kDistillStatWords] = {};
+  if (!rc) {
+    memcpy(&s, back.data(), 8);
+    memcpy(stats, back.data() + (lay.stats - lay.back), sizeof stats);
+    if (!distill_stats_sane(stats, m, s))
+      rc = fail(e, NGPU_EHIP, "dict distill: %llu survivors, %llu digests of %llu records",
+                (unsigned long long)s, (unsigned long long)stats[kDistillDistinct], (unsigned long long)m);
+  }
+  if (!rc) {
+    res->plan = distill_blob_plan(nb0, reinterpret_cast<const uint32_t *>(back.data() + (lay.live - lay.back)),
+                                  flags, table.size() >= 256ull * nb0 && nb0 ? table.data() : nullptr);
+    distill_info_fill(&res->info, m, stats, nb0, res->plan.n_kept);
+    res->s = s;
+  }
+  if (!rc && want_out) {
+    if (nb0 && hipMemcpyAsync(d_remap, res->plan.remap.data(), 4ull * nb0, hipMemcpyHostToDevice, bs.s) !=
+                   hipSuccess)
+      rc = fail(e, NGPU_EHIP, "dict distill: upload failed");
+    if (!rc)
+      rc = dict_compact_tail(e, "dict distill", base, bs.s, d_words, d_cnt, d_remap, s, place, hk, tr, 3,
+                             &dst);
+  }
+  if (rc && hipStreamSynchronize(bs.s) != hipSuccess)
+    (void)hipGetLastError();  // (nothing of the stream still reads the scratch)
+  const double a = rc ? -1.0 : tr.us(0, 1), b = rc ? -1.0 : tr.us(1, 2),
+               c = rc || !want_out ? 0.0 : tr.us(3, 4);
+  if (a >= 0 && b >= 0 && c >= 0)
+    fprintf(stderr,
+            "ngpu dict_distill m=%llu s=%llu device_us=%.1f count_us=%.1f keep_scan_us=%.1f "
+            "compact_build_us=%.1f\n",
+            (unsigned long long)m, (unsigned long long)s, a + b + c, a, b, c);
+  (void)hipFree(scr);
+  if (rc) return rc;
+  if (want_out) *out = dict_compact_handle(base, dst, s, res->plan.n_kept, place != nullptr);
+  return 0;
+}
+
+int dict_distill_args(uint32_t flags) {
+  const uint32_t both = NGPU_DICT_DISTILL_KEEP_BLOBS | NGPU_DICT_DISTILL_MERGE_BLOB_IDS;
+  return (flags & ~both) || (flags & both) == both ? NGPU_EINVAL : 0;
 }
 
 void dict_export_row(const DictRec &r, const DictPlace *row, uint8_t *dst) {
@@ -1032,6 +1165,29 @@ int ngpu_dict_retire(ngpu_engine *e, ngpu_dict *base, const uint32_t *blobs, uin
       return rc;
     d->blob_table = dict_retire_blob_table(base->blob_table, plan.remap);
     *out = d;
+    return 0;
+  });
+}
+
+int ngpu_dict_distill(ngpu_engine *e, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                      ngpu_dict **out, ngpu_dict_distill_info *info) {
+  if (out) *out = nullptr;
+  if (info) memset(info, 0, sizeof *info);
+  if (!base || !e || dict_distill_args(flags)) return NGPU_EINVAL;
+  return guarded([&]() -> int {
+    if (int rc = dict_plain_base_check(e, base, "dict distill",
+                                       "a node dict is distilled with ngpu_node_dict_distill"))
+      return rc;
+    if ((flags & NGPU_DICT_DISTILL_MERGE_BLOB_IDS) && base->dev.m && base->blob_table.empty())
+      return fail(e, NGPU_EINVAL, "dict distill: blob ids are merged by the blob table, the dict has none");
+    DictDistilled res;
+    ngpu_dict *d = nullptr;
+    if (int rc = dict_distill_records(e, base, base->blob_table, min_refs, flags, base->place(), nullptr,
+                                      out != nullptr, &res, &d))
+      return rc;
+    if (d) d->blob_table = dict_retire_blob_table(base->blob_table, res.plan.rows);
+    if (out) *out = d;
+    if (info) *info = res.info;
     return 0;
   });
 }

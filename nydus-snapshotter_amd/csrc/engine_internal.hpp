@@ -12,6 +12,7 @@
 
 #include "blob.hpp"
 #include "common.hpp"
+#include "dict_distill_plan.hpp"
 
 // Pinned staging + device buffers of one streaming-Pack slot, kept by the
 // engine between packs (pinning 64 MiB costs milliseconds: per-pack
@@ -471,6 +472,22 @@ void dict_retire_place(const DictKeep &keep, uint64_t m, const DictPlace *src, D
 // The blob table rows of the kept blobs, in order (empty table: empty).
 std::vector<uint8_t> dict_retire_blob_table(const std::vector<uint8_t> &table,
                                             const std::vector<uint32_t> &remap);
+// Dict distill (dict.hip): dict_retire_records with keep bits from the rows' own
+// digests: a row stays when it is the first of its digest and at least
+// max(min_refs, 1) rows of base hold it.  flags: NGPU_DICT_DISTILL_*, checked by
+// dict_distill_args (0 or NGPU_EINVAL); table: the 256-B blob rows MERGE_BLOB_IDS
+// compares.  res: the survivor count, the info and what becomes of the blobs
+// (the caller filters its blob table by res->plan.rows).  want_out false: counts
+// only, nothing is allocated for a result and *out is not written.
+struct DictDistilled {
+  uint64_t s = 0;
+  ngpu_dict_distill_info info;
+  DistillBlobPlan plan;
+};
+int dict_distill_args(uint32_t flags);
+int dict_distill_records(ngpu_engine *e, const ngpu_dict *base, const std::vector<uint8_t> &table,
+                         uint32_t min_refs, uint32_t flags, const DictPlace *place, DictKeep *keep,
+                         bool want_out, DictDistilled *res, ngpu_dict **out);
 int read_dict_bootstrap(ngpu_engine *e, const char *path, uint64_t file_size,
                         std::vector<uint8_t> *recs_out, std::vector<uint8_t> *blobs_out,
                         uint64_t *table_at = nullptr);

@@ -434,6 +434,71 @@ int node_dict_retire(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, ui
   return 0;
 }
 
+// base with one row per digest (dict.hip "dict distill"): every replica distilled
+// alike, the global placement rows compacted by part 0's keep words, as
+// node_dict_retire does.  want_out false: the counts of part 0 alone.
+int node_dict_distill(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                      ngpu_dict **out, ngpu_dict_distill_info *info) {
+  ngpu_engine *e0 = node->eng[0];
+  const uint32_t W = (uint32_t)node->eng.size();
+  if (int rc = node_dict_base_check(node, base, "distill")) return rc;
+  if ((flags & NGPU_DICT_DISTILL_MERGE_BLOB_IDS) && base->dev.m && base->blob_table.empty())
+    return fail(e0, NGPU_EINVAL,
+                "node dict distill: blob ids are merged by the blob table, the dict has none");
+  if (!base->replicated)
+    return fail(e0, NGPU_EUNSUPP,
+                "node dict distill: partitioned node dicts are not supported yet (replicated ones are)");
+  DictDistilled res;
+  if (!out) {
+    if (int rc = dict_distill_records(e0, base->parts[0], base->blob_table, min_refs, flags, nullptr,
+                                      nullptr, false, &res, nullptr))
+      return rc;
+    if (info) *info = res.info;
+    return 0;
+  }
+  ngpu_dict *d = dict_derive(base);
+  DictKeep keep;
+  int rc = 0;
+  for (uint32_t o = 0; o < W && !rc; ++o) {
+    ngpu_dict *p = nullptr;
+    DictDistilled r;
+    if ((rc = dict_distill_records(node->eng[o], base->parts[o], base->blob_table, min_refs, flags,
+                                   nullptr, o == 0 ? &keep : nullptr, true, &r, &p)))
+      break;
+    if (o == 0) res = r;
+    if (o && (p->dev.m != d->parts[0]->dev.m || p->dev.n_blobs != d->parts[0]->dev.n_blobs)) {
+      dict_unref(p);
+      rc = fail(e0, NGPU_EINVAL, "node dict distill: the replicas differ");
+      break;
+    }
+    d->parts.push_back(p);
+  }
+  if (!rc) {
+    const uint64_t m = base->dev.m, s = res.s;
+    d->dev.m = s;
+    d->dev.n_blobs = res.plan.n_kept;
+    // the global handle: placement rows only (if base keeps any), with a fork's room
+    const DictPlace *rows = base->place();
+    const uint64_t cap = dict_retire_rec_cap(s);
+    if (!(rc = storage_alloc_place_only(e0, rows && s ? cap : 0, &d->st))) {
+      d->st->rec_cap = cap;
+      d->st->used = s;
+      if (rows && s) {
+        dict_retire_place(keep, m, rows, d->st->place, s);
+        d->has_place = true;
+      }
+    }
+  }
+  if (rc) {
+    dict_unref(d);
+    return rc;
+  }
+  d->blob_table = dict_retire_blob_table(base->blob_table, res.plan.rows);
+  *out = d;
+  if (info) *info = res.info;
+  return 0;
+}
+
 // ---- node dict retire across parts ---------------------------------------------
 // ngpu_node_dict_retire_parts: the retire of a partitioned dict.  The parts tile
 // the old global ids [0, m); a part's new global ids are ranks over all parts'
@@ -1416,6 +1481,20 @@ int ngpu_node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t
   if (out) *out = nullptr;
   if (!base || flags || !node || !out || (n && !blobs)) return NGPU_EINVAL;
   return guarded([&] { return node_dict_retire_parts(node, base, blobs, n, out); });
+}
+
+int ngpu_node_dict_distill(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                           ngpu_dict **out, ngpu_dict_distill_info *info) {
+  if (out) *out = nullptr;
+  if (info) memset(info, 0, sizeof *info);
+  if (!base || !node || dict_distill_args(flags)) return NGPU_EINVAL;
+  return guarded([&]() -> int {
+    ngpu_dict_distill_info got;
+    memset(&got, 0, sizeof got);
+    const int rc = node_dict_distill(node, base, min_refs, flags, out, &got);
+    if (!rc && info) *info = got;
+    return rc;
+  });
 }
 
 int ngpu_node_dict_export(ngpu_node *node, const ngpu_dict *d, void *records, uint64_t cap,

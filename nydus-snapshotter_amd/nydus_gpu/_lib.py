@@ -94,7 +94,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # node dict retire / export across parts (additive in ABI 7)
            "ngpu_node_dict_retire_parts", "ngpu_node_dict_export",
            # dict save (additive in ABI 7)
-           "ngpu_dict_save_layout", "ngpu_dict_save", "ngpu_node_dict_save"]
+           "ngpu_dict_save_layout", "ngpu_dict_save", "ngpu_node_dict_save",
+           # dict distill (additive in ABI 7)
+           "ngpu_dict_distill", "ngpu_node_dict_distill"]
 
 # ngpu_dict_place: the compressed placement of one folded record (host rows)
 DICT_PLACE_DTYPE = np.dtype([("compressed_offset", "<u8"), ("compressed_size", "<u4"), ("flags", "<u4")])
@@ -127,6 +129,33 @@ class NgpuDictSaveInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(NgpuDictSaveOptions) == 40 and ctypes.sizeof(NgpuDictSaveInfo) == 64
+
+DICT_DISTILL_KEEP_BLOBS = 0x1
+DICT_DISTILL_MERGE_BLOB_IDS = 0x2
+
+
+class NgpuDictDistillInfo(ctypes.Structure):
+    _fields_ = [("entries_in", ctypes.c_uint64), ("distinct", ctypes.c_uint64),
+                ("shadowed", ctypes.c_uint64), ("below_min", ctypes.c_uint64),
+                ("entries_out", ctypes.c_uint64), ("blobs_in", ctypes.c_uint32),
+                ("blobs_out", ctypes.c_uint32), ("max_refs", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("refs_hist", ctypes.c_uint64 * 32)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("reserved", "refs_hist")}
+        d["refs_hist"] = [int(x) for x in self.refs_hist]
+        return d
+
+
+assert ctypes.sizeof(NgpuDictDistillInfo) == 312
+
+
+def _dict_distill(call, check, what, min_refs, keep_blobs, merge_blob_ids, count_only):
+    """The two distill calls: call(min_refs, flags, out, info) -> rc."""
+    flags = (DICT_DISTILL_KEEP_BLOBS if keep_blobs else 0) | (DICT_DISTILL_MERGE_BLOB_IDS if merge_blob_ids else 0)
+    h, info = ctypes.c_void_p(), NgpuDictDistillInfo()
+    check(call(int(min_refs), flags, None if count_only else ctypes.byref(h), ctypes.byref(info)), what)
+    return (None if count_only else h), info.as_dict()
 
 
 LAYER_STATS_DTYPE = np.dtype([("chunks", "<u8"), ("new_chunks", "<u8"), ("intra_chunks", "<u8"),
@@ -370,6 +399,8 @@ def lib():
     L.ngpu_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32)]
     L.ngpu_node_dict_retire_parts.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.ngpu_node_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32), u32]
+    L.ngpu_dict_distill.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(NgpuDictDistillInfo)]
+    L.ngpu_node_dict_distill.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(NgpuDictDistillInfo)]
     L.ngpu_dict_save_layout.argtypes = [u64, u32, ctypes.POINTER(NgpuDictSaveInfo)]
     L.ngpu_dict_save.argtypes = [vp, vp, ctypes.POINTER(NgpuDictSaveOptions), WRITE_FN, vp,
                                  ctypes.POINTER(NgpuDictSaveInfo)]
@@ -894,6 +925,19 @@ class ChunkDict:
         e._check(lib().ngpu_dict_retire(e._h, self._h, _ptr(idx) if len(idx) else None, len(idx), 0,
                                         ctypes.byref(h)), "dict_retire")
         return ChunkDict(h, e)
+
+    def distill(self, min_refs: int = 1, *, keep_blobs: bool = False, merge_blob_ids: bool = False,
+                count_only: bool = False):
+        """ngpu_dict_distill: (a new dict of the first row of every digest that at
+        least max(min_refs, 1) rows of this one hold, or None with count_only;
+        the info as a dict: entries_in, distinct, shadowed, below_min, entries_out,
+        blobs_in, blobs_out, max_refs, refs_hist).  Blobs without a surviving row
+        leave unless keep_blobs; merge_blob_ids maps blobs whose table rows repeat
+        a blob id to the first of them.  This handle stays as it is."""
+        e = self._engine()
+        h, info = _dict_distill(lambda *a: lib().ngpu_dict_distill(e._h, self._h, *a), e._check,
+                                "dict_distill", min_refs, keep_blobs, merge_blob_ids, count_only)
+        return (None if h is None else ChunkDict(h, e)), info
 
     def _engine(self):
         if self._eng is None or not self._eng._h:
@@ -1663,6 +1707,14 @@ class Node:
         self._err(lib().ngpu_node_dict_retire(self._h, base._h, _ptr(idx), len(idx), 0,
                                               ctypes.byref(h)), "node_dict_retire")
         return ChunkDict(h)
+
+    def dict_distill(self, base: ChunkDict, min_refs: int = 1, *, keep_blobs: bool = False,
+                     merge_blob_ids: bool = False, count_only: bool = False):
+        """ngpu_node_dict_distill: ChunkDict.distill for (replicated) node dicts;
+        a partitioned one raises NgpuError (EUNSUPP)."""
+        h, info = _dict_distill(lambda *a: lib().ngpu_node_dict_distill(self._h, base._h, *a), self._err,
+                                "node_dict_distill", min_refs, keep_blobs, merge_blob_ids, count_only)
+        return (None if h is None else ChunkDict(h)), info
 
     def dict_export_parts(self, d: ChunkDict):
         """ngpu_node_dict_export: (records as rafs.CHUNK_INFO_DTYPE in global table

@@ -18,9 +18,9 @@ usage:
   python -m nydus_gpu.inspect --tree FILE     # JSON dump of the inode tree
   python -m nydus_gpu.inspect --diff A B      # exit 0 iff the chunk sets match
   python -m nydus_gpu.inspect --diff --tree A B  # exit 0 iff the trees match
-  python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP]... [--retire BLOBID]... [--chunk-size N] [--digester D]
+  python -m nydus_gpu.inspect --check STREAM [--dict BOOTSTRAP]... [--retire BLOBID]... [--distill [N]] [--merge-blob-ids] [--chunk-size N] [--digester D]
                                               # re-digest STREAM's chunks on the GPU; exit 1 if any is bad
-  python -m nydus_gpu.inspect --dict BOOTSTRAP [--dict BOOTSTRAP]... [--retire BLOBID]... --save-dict OUT
+  python -m nydus_gpu.inspect --dict BOOTSTRAP [--dict BOOTSTRAP]... [--retire BLOBID]... [--distill [N]] [--merge-blob-ids] --save-dict OUT
                                               # fold the dict bootstraps on the GPU and write the result to OUT
   python -m nydus_gpu.inspect --verity IMAGE [--append]
                                               # the dm-verity tree of a block image; prints its options line
@@ -40,11 +40,17 @@ conversion run folds each converted image into its chunk dict.
 Every `--retire BLOBID` (64 hex characters, or an inner blob index) then drops
 that blob's records from the folded dict (ChunkDict.retire), as a registry's
 garbage collection does: DICT records of a retired blob no longer resolve.
+`--distill [N]` (default 1; ChunkDict.distill, ngpu_dict_distill) then keeps one
+row per digest, the first, and only the digests that at least N rows held: a
+dict folded from converted layers repeats every chunk a layer reused, and those
+rows can never answer.  Blobs left without a row leave; `--merge-blob-ids` also
+maps blobs whose table rows repeat a blob id to the first of them (it implies
+`--distill`).  The report gains "distill": the info fields.
 The digester, chunk size and RAFS version default to the stream's own; the
 report is printed as JSON.
 
 `--save-dict OUT` (ChunkDict.save, ngpu_dict_save) needs a GPU: the dict folded
-from the `--dict` files, after any `--retire`, is written to OUT as a RAFS v6 dict
+from the `--dict` files, after any `--retire` and `--distill`, is written to OUT as a RAFS v6 dict
 bootstrap that `--dict`, ngpu_dict_open and Merge read.  With `--check` the
 report gains "saved_dict": {path, entries, blobs, bytes}; without it the command
 stands alone, takes chunk size and digester from the first `--dict` bootstrap
@@ -160,9 +166,10 @@ def diff(a: dict, b: dict, fields=("digest", "blob_id", "uncompressed_size")) ->
     return [("-", k) for k in sorted(ka - kb)] + [("+", k) for k in sorted(kb - ka)]
 
 
-def folded_dict(eng, dict_path=None, retire=None):
+def folded_dict(eng, dict_path=None, retire=None, distill=None, merge_blob_ids=False, report=None):
     """The dict of the --dict bootstraps on `eng`: the first opened, each further
-    one appended, then the --retire blobs (ids or inner indices) dropped.  None
+    one appended, then the --retire blobs (ids or inner indices) dropped, then
+    (distill: min_refs, or None) distilled, its info into report["distill"].  None
     without a --dict; the caller releases it."""
     paths = [dict_path] if isinstance(dict_path, str) else list(dict_path or [])
     dct = eng.dict_open(paths[0]) if paths else None
@@ -177,6 +184,16 @@ def folded_dict(eng, dict_path=None, retire=None):
             kept = dct.retire([int(b) if str(b).isdigit() and len(str(b)) < 64 else b for b in retire])
             dct.release()
             dct = kept
+        if merge_blob_ids and distill is None:
+            distill = 1
+        if distill is not None:
+            if dct is None:
+                raise ValueError("--distill needs a --dict")
+            kept, info = dct.distill(distill, merge_blob_ids=merge_blob_ids)
+            dct.release()
+            dct = kept
+            if report is not None:
+                report["distill"] = info
         return dct
     except BaseException:
         if dct is not None:
@@ -191,10 +208,12 @@ def _save(dct, out: str) -> dict:
     return {"path": out, "entries": info["entries"], "blobs": info["blobs"], "bytes": info["bytes"]}
 
 
-def save_dict(out: str, dict_path, chunk_size: int = 0, digester: str = None, retire=None) -> dict:
-    """The dict folded from the --dict bootstraps (after any --retire) written to
-    `out` with ChunkDict.save on GPU 0 -> {path, entries, blobs, bytes}.  Chunk
-    size and digester default to the first bootstrap's."""
+def save_dict(out: str, dict_path, chunk_size: int = 0, digester: str = None, retire=None, distill=None,
+              merge_blob_ids: bool = False) -> dict:
+    """The dict folded from the --dict bootstraps (after any --retire and distill)
+    written to `out` with ChunkDict.save on GPU 0 -> {path, entries, blobs, bytes},
+    and "distill": the info of a distill.  Chunk size and digester default to the
+    first bootstrap's."""
     from ._lib import Engine
     paths = [dict_path] if isinstance(dict_path, str) else list(dict_path or [])
     if not paths:
@@ -206,18 +225,21 @@ def save_dict(out: str, dict_path, chunk_size: int = 0, digester: str = None, re
     flags, _, _, cs = struct.unpack_from("<QQII", head, rafs.EXT_OFFSET)
     with Engine(device=0, digester=digester or ("sha256" if flags & 0x8 else "blake3"),
                 chunk_size=chunk_size or cs, fs_version=6) as eng:
-        dct = folded_dict(eng, paths, retire)
+        extra = {}
+        dct = folded_dict(eng, paths, retire, distill, merge_blob_ids, extra)
         try:
-            return _save(dct, out)
+            return dict(_save(dct, out), **extra)
         finally:
             dct.release()
 
 
 def check(path: str, dict_path=None, chunk_size: int = 0, digester: str = None,
-          max_bad: int = 64, retire=None, save_dict: str = None) -> dict:
+          max_bad: int = 64, retire=None, save_dict: str = None, distill=None,
+          merge_blob_ids: bool = False) -> dict:
     """Engine.check of the stream in `path` on GPU 0 (the report dict).
     dict_path: a chunk-dict bootstrap, or a list of them folded into one dict;
     retire: blob ids (or inner indices) whose records leave the folded dict first;
+    distill: min_refs of a ChunkDict.distill after that (None: none), reported as "distill";
     save_dict: write that dict there (ChunkDict.save), reported as "saved_dict"."""
     from ._lib import Engine
     data = np.fromfile(path, np.uint8)
@@ -231,10 +253,12 @@ def check(path: str, dict_path=None, chunk_size: int = 0, digester: str = None,
         flags, cs = int(d["flags"]), int(d["chunk_size"])
     with Engine(device=0, digester=digester or ("sha256" if flags & 0x8 else "blake3"),
                 chunk_size=chunk_size or cs, fs_version=6 if v6 else 5) as eng:
-        dct = folded_dict(eng, dict_path, retire)
+        extra = {}
+        dct = folded_dict(eng, dict_path, retire, distill, merge_blob_ids, extra)
         try:
             saved = _save(dct, save_dict) if save_dict else None
             rep = eng.check(data, dict=dct, max_bad=max_bad)
+            rep.update(extra)
             if saved is not None:
                 rep["saved_dict"] = saved
             return rep
@@ -309,6 +333,10 @@ def main(argv=None) -> int:
                     help="--check: chunk-dict bootstrap for DICT records (repeat to fold several into one dict)")
     ap.add_argument("--retire", metavar="BLOBID", action="append",
                     help="--check: drop this blob's records from the folded dict first (repeatable)")
+    ap.add_argument("--distill", metavar="N", type=lambda x: int(x, 0), nargs="?", const=1, default=None,
+                    help="then keep one row per digest, of the digests at least N rows held (default 1)")
+    ap.add_argument("--merge-blob-ids", action="store_true",
+                    help="--distill: blobs whose table rows repeat a blob id become the first of them")
     ap.add_argument("--save-dict", metavar="OUT",
                     help="write the dict folded from the --dict files (after any --retire) to OUT as a "
                          "RAFS v6 dict bootstrap; with --check the report names it, alone it prints "
@@ -334,7 +362,7 @@ def main(argv=None) -> int:
             pass
         try:
             rep = check(args.check, args.dict, args.chunk_size, args.digester, retire=args.retire,
-                        save_dict=args.save_dict)
+                        save_dict=args.save_dict, distill=args.distill, merge_blob_ids=args.merge_blob_ids)
         except (NgpuError, ValueError, OSError) as e:
             print(f"check: {e}", file=sys.stderr)
             return 2
@@ -347,7 +375,8 @@ def main(argv=None) -> int:
         except ImportError:
             pass
         try:
-            rep = save_dict(args.save_dict, args.dict, args.chunk_size, args.digester, retire=args.retire)
+            rep = save_dict(args.save_dict, args.dict, args.chunk_size, args.digester, retire=args.retire,
+                            distill=args.distill, merge_blob_ids=args.merge_blob_ids)
         except (NgpuError, ValueError, OSError) as e:
             print(f"save-dict: {e}", file=sys.stderr)
             return 2
