@@ -853,13 +853,55 @@ int ngpu_node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t
 /* ngpu_dict_distill for node dicts (additive in ABI 7), with its contract, flags
  * and info.  A replicated dict distils every replica alike, with one result and
  * the node handle's placement rows following: the way ngpu_node_dict_retire goes
- * (out == NULL counts on the first replica alone).  A partitioned dict is
- * NGPU_EUNSUPP for now: all rows of a digest live on one part, so the counting is
- * local, but the global ranks and the union of live blobs need the exchange of
- * ngpu_node_dict_retire_parts.  A plain dict, or a dict of another node, is
- * NGPU_EINVAL.  *out is NULL and info zeroed on every failure. */
+ * (out == NULL counts on the first replica alone).  A partitioned dict returns
+ * NGPU_EUNSUPP from this call, as it always has: ngpu_node_dict_distill_parts
+ * distils both modes.  A plain dict, or a dict of another node, is NGPU_EINVAL.
+ * *out is NULL and info zeroed on every failure. */
 int ngpu_node_dict_distill(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
                            ngpu_dict **out, ngpu_dict_distill_info *info);
+/* ngpu_dict_distill for node dicts of both modes (additive in ABI 7).  A replicated
+ * dict goes the way of ngpu_node_dict_distill.  For a partitioned dict the contract
+ * is ngpu_dict_distill's, stated on the whole dict: out answers every probe, Pack,
+ * ngpu_node_process_device / _step, export and save as ngpu_node_dict_create does,
+ * in base's mode and exchange, over the winners of base (the first row of every
+ * digest in global table order) that at least max(min_refs, 1) rows hold, in global
+ * table order, with the blob rows as the flags say (the default,
+ * NGPU_DICT_DISTILL_KEEP_BLOBS and NGPU_DICT_DISTILL_MERGE_BLOB_IDS mean and refuse
+ * what they do for ngpu_dict_distill).  Entry ids (the global ids the parts' hits
+ * carry) are positions among ALL parts' survivors; the node handle's placement rows
+ * follow iff base kept them.  All rows of a digest live on one part, so every part
+ * counts its own rows; a blob is live if ANY part holds a survivor in it.  Only the
+ * handle's own entries(base) count: rows a later in-place extend or fold appended
+ * to the parts' storages are not seen.  base is only read: probes, Packs and
+ * in-place extends of it may run meanwhile.
+ *
+ * info is over the whole dict: entries_in = entries(base); distinct, below_min and
+ * every refs_hist bucket are the sums over the parts, max_refs their maximum,
+ * blobs_in and blobs_out the dict's.  It is filled on success and zeroed on every
+ * failure.  out == NULL only counts: every part counts, no storage is allocated and
+ * info (blobs_out included) is that of a full call.
+ *
+ * Every part of out sits on a storage of its own with ngpu_dict_retire's room for
+ * its own survivors (s + s / 2 record slots), the node handle on placement rows
+ * for all of them, so later extends and folds append in place.  A min_refs above
+ * every count gives a valid dict of 0 entries and 0 blobs, which can be extended.
+ * The device work runs on streams of the library's own, one per part, which
+ * exchange one keep bit per entry of base between the parts (W x entries / 8 bytes
+ * into every part); all parts are enqueued before the call's one mid-way wait, and
+ * all streams are synchronised when the call returns, on every path.
+ *
+ * Rejected before any GPU work, with *out = NULL and info zeroed: a NULL node or
+ * base, flag bits other than the two or both together, MERGE_BLOB_IDS on a dict
+ * with records and no blob table, a plain dict, a dict of another node, parts whose
+ * row counts do not add up to entries(base) (NGPU_EINVAL).  Parts whose surviving
+ * global ids do not tile [0, entries(base)) -- an id past the end or held twice --
+ * are NGPU_EINVAL before anything is allocated.
+ *
+ * UNVERIFIED ON DISTINCT GPUs, as the node exchange above: every test so far
+ * lists one GPU several times. */
+int ngpu_node_dict_distill_parts(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                                 ngpu_dict **out /* NULL: count only */,
+                                 ngpu_dict_distill_info *info /* may be NULL */);
 /* ngpu_dict_export for node dicts of both modes (additive in ABI 7), with its
  * contract: *n_records and *n_blobs are always set, records == NULL && cap == 0
  * only counts, cap < entries(d) or too few blob_cap rows is NGPU_EINVAL with

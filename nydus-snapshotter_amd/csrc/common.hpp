@@ -368,6 +368,17 @@ void launch_node_split(const DictRec *rows, uint64_t k, uint32_t W, uint32_t *cn
 void launch_node_keep_scan(const DictRec *rec, uint64_t m_o, const uint32_t *bitmap, uint32_t n_blobs,
                            uint64_t m, uint64_t *words, uint32_t *cnt, uint64_t *sums, uint64_t *gbits,
                            uint64_t *ctr, hipStream_t s);
+// node_distill.hip (ngpu_node_dict_distill_parts, node.hip; node_distill_plan.hpp
+// lays the scratch out).  Per part, after launch_dict_ref_count over its own rows
+// and table: launch_distill_keep_scan and launch_node_keep_scan in one pass -- the
+// keep words (refs[i] >= max(min_refs, 1)), prefixes and s_o, the live blobs and
+// the kDistillStatWords counters of the first, bit gid of gbits and the two
+// counters of ctr (kNodeRetireBadGid, kNodeRetireDupBit) of the second.  live,
+// stats, gbits and ctr are zeroed on s by the caller.
+void launch_node_distill_keep_scan(const DictRec *rec, uint64_t m_o, const uint32_t *refs, uint32_t min_refs,
+                                   uint32_t n_blobs, uint64_t m, uint64_t *words, uint32_t *cnt,
+                                   uint64_t *sums, uint32_t *live, uint64_t *stats, uint64_t *gbits,
+                                   uint64_t *ctr, hipStream_t s);
 // gather: the W parts' bitmaps, part p's (m + 63) / 64 words at p * that many.
 // Their OR to gwords, its popcounts scanned in gcnt (gsums: the scan's sums, S
 // last), words set by two parts counted; then *s_local and S into ctr.

@@ -29,11 +29,7 @@ namespace {
 // count of a hot digest, the counters) is carried over its tiles and leaves
 // once, so the atomics on one address go with the number of workgroups, not with
 // the number of waves (16 M rows: 250,000 waves, 2,048 workgroups).
-constexpr uint64_t kDistillGrid = 2048;
-__host__ __device__ inline uint64_t distill_tiles_per_wg(uint64_t m) {
-  const uint64_t per = ((m + 255) / 256 + kDistillGrid - 1) / kDistillGrid;
-  return per < 4 ? 4 : per;
-}
+// (distill_tiles_per_wg: dict_distill_plan.hpp; node_distill.hip runs by it too.)
 
 // refs[key] += 1 for the lanes with act set.  Rows of one digest often sit in one
 // wave (a zero chunk in every layer, a layer extended twice): the lanes that

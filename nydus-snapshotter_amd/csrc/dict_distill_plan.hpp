@@ -28,6 +28,14 @@ constexpr int kDistillStatWords = kDistillHist + 32;
 // refs >= 1 -> the bucket b with 2^b <= refs < 2^(b + 1).
 NGPU_HD uint32_t distill_bucket(uint32_t refs) { return 31u - (uint32_t)__builtin_clz(refs | 1u); }
 
+// The 256-row tiles a workgroup of the distill kernels runs over: at least 4, and
+// as many as it takes for kDistillGrid workgroups to cover the dict.
+constexpr uint64_t kDistillGrid = 2048;
+inline uint64_t distill_tiles_per_wg(uint64_t m) {
+  const uint64_t per = ((m + 255) / 256 + kDistillGrid - 1) / kDistillGrid;
+  return per < 4 ? 4 : per;
+}
+
 inline uint64_t distill_live_words(uint32_t n_blobs) { return n_blobs ? (n_blobs + 31) / 32 : 1; }
 
 // A distill's one scratch allocation, byte offsets.  words / sums / cnt are the

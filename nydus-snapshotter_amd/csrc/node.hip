@@ -41,6 +41,7 @@
 #include "a2a_plan.hpp"
 #include "dict_retire_plan.hpp"
 #include "engine_internal.hpp"
+#include "node_distill_plan.hpp"
 #include "node_fold_plan.hpp"
 #include "node_retire_plan.hpp"
 
@@ -524,96 +525,276 @@ int node_dict_distill(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint3
 struct RetirePart {
   std::unique_ptr<BuildStream> bs;
   hipEvent_t ready = nullptr;  // its bitmap is complete
-  hipEvent_t t[5] = {};        // NGPU_DICT_TRACE=1: keep, gather + merge, compact + build
+  hipEvent_t t[6] = {};        // NGPU_DICT_TRACE=1: the ends of the call's device phases
   uint8_t *scr = nullptr;
   NodeRetireScratch lay;
   uint64_t m_o = 0;
   DictStorage *dst = nullptr;
 };
 
+// What node_dict_retire_parts and node_dict_distill_parts (below) share: the
+// parts' streams, events and scratch, steps 2, 4 and 5 above, and the waits and
+// releases of every path.  what: "node dict retire"; sym: the trace lines' name.
+struct PartsCall {
+  ngpu_node *node;
+  ngpu_dict *base;
+  const char *what, *sym;
+  ngpu_engine *e0;
+  const uint32_t W;
+  const uint64_t m, gnw;
+  const uint32_t nb0;
+  const DictPlace *rows;
+  bool trace;
+  // the trace's host side: milliseconds since the call began at the end of each phase
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  double t_host[5] = {};
+  std::vector<RetirePart> pt;
+  // the engines' kept pinned counter words (fold_h, under fold_mu in index order as
+  // node_dict_fold takes them): a pinned allocation per call costs milliseconds
+  std::vector<std::unique_lock<std::mutex>> lanes;
+  DictKeep keep;
+  int rc = 0;
+
+  PartsCall(ngpu_node *node_, ngpu_dict *base_, const char *what_, const char *sym_)
+      : node(node_), base(base_), what(what_), sym(sym_), e0(node_->eng[0]),
+        W((uint32_t)node_->eng.size()), m(base_->dev.m), gnw((base_->dev.m + 63) / 64),
+        nb0(base_->dev.n_blobs), rows(base_->place()), pt(node_->eng.size()) {
+    const char *tv = getenv("NGPU_DICT_TRACE");
+    trace = tv && tv[0] == '1';
+  }
+  void stamp(int i) {
+    if (trace)
+      t_host[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  void mark(RetirePart &p, int i) {
+    if (trace && p.t[i]) (void)hipEventRecord(p.t[i], p.bs->s);
+  }
+  int pinned() {
+    for (uint32_t o = 0; o < W; ++o) lanes.emplace_back(node->eng[o]->fold_mu);
+    for (uint32_t o = 0; o < W; ++o) {
+      ngpu_engine *e = node->eng[o];
+      DeviceGuard dg(e->device);
+      if (!e->fold_h && hipHostMalloc((void **)&e->fold_h, 512) != hipSuccess) {
+        (void)hipGetLastError();
+        e->fold_h = nullptr;
+        return fail(e0, NGPU_ENOMEM, "%s: pinned counters", what);
+      }
+    }
+    return 0;
+  }
+  // Part o's stream, events (n_events of the trace's) and scratch of lay.bytes;
+  // the caller holds a DeviceGuard of the part's device.  Sets rc on failure.
+  bool part_begin(uint32_t o, const NodeRetireScratch &lay, int n_events) {
+    RetirePart &p = pt[o];
+    p.m_o = base->parts[o]->dev.m;
+    p.lay = lay;
+    p.bs.reset(new BuildStream(node->dev[o]));
+    if (!p.bs->s || hipEventCreateWithFlags(&p.ready, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(e0, NGPU_EHIP, "%s: part %u: no build stream", what, o);
+      return false;
+    }
+    for (int i = 0; trace && i < n_events; ++i)
+      if (hipEventCreate(&p.t[i]) != hipSuccess) p.t[i] = nullptr;
+    if (hipMalloc((void **)&p.scr, p.lay.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      p.scr = nullptr;
+      rc = fail(e0, NGPU_ENOMEM, "%s: part %u: scratch allocation failed", what, o);
+      return false;
+    }
+    return true;
+  }
+  void quiesce() {  // every stream the call used, whatever another one said
+    for (uint32_t o = 0; o < W; ++o) {
+      if (!pt[o].bs || !pt[o].bs->s) continue;
+      DeviceGuard dg(node->dev[o]);
+      if (hipStreamSynchronize(pt[o].bs->s) != hipSuccess && !rc)
+        rc = fail(e0, NGPU_EHIP, "%s: part %u failed on its device", what, o);
+    }
+  }
+  void release() {  // after quiesce(): the scratch, the events, storages not handed over
+    for (uint32_t o = 0; o < W; ++o) {
+      RetirePart &p = pt[o];
+      DeviceGuard dg(node->dev[o]);
+      if (p.scr) (void)hipFree(p.scr);
+      p.scr = nullptr;
+      if (p.ready) (void)hipEventDestroy(p.ready);
+      p.ready = nullptr;
+      for (hipEvent_t &ev : p.t) {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+      }
+      storage_unref(p.dst);
+      p.dst = nullptr;
+    }
+  }
+  // Step 2 on every part (rc == 0, every part's ready recorded): the all-gather of
+  // the bitmaps, their OR and the global scan; ctr_words words from the part's
+  // counter block go to its engine's pinned words, and part 0 brings the global
+  // keep words and prefixes back when base keeps placement rows.  ev: the trace
+  // event after the merge.
+  void gather_merge(int ctr_words, int ev) {
+    for (uint32_t o = 0; o < W && !rc; ++o) {
+      RetirePart &p = pt[o];
+      DeviceGuard dg(node->dev[o]);
+      const hipStream_t s = p.bs->s;
+      bool ok = true;
+      for (uint32_t q = 0; q < W && ok && gnw; ++q) {
+        uint8_t *to = p.scr + p.lay.gather + 8 * gnw * q;
+        const uint8_t *from = pt[q].scr + pt[q].lay.own;
+        if (q == o)  // written on this very stream
+          ok = hipMemcpyAsync(to, from, 8 * gnw, hipMemcpyDeviceToDevice, s) == hipSuccess;
+        else
+          ok = hipStreamWaitEvent(s, pt[q].ready, 0) == hipSuccess &&
+               hipMemcpyPeerAsync(to, node->dev[o], from, node->dev[q], 8 * gnw, s) == hipSuccess;
+      }
+      if (ok) {
+        uint64_t *d_ctr = (uint64_t *)(p.scr + p.lay.ctr);
+        launch_node_keep_merge((const uint64_t *)(p.scr + p.lay.gather), W, m,
+                               (uint64_t *)(p.scr + p.lay.gwords), (uint32_t *)(p.scr + p.lay.gcnt),
+                               (uint64_t *)(p.scr + p.lay.gsums),
+                               (const uint64_t *)(p.scr + p.lay.sums) + dict_retire_scan_tiles(p.m_o), d_ctr,
+                               s);
+        mark(p, ev);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(node->eng[o]->fold_h, d_ctr, 8 * (size_t)ctr_words, hipMemcpyDeviceToHost, s) ==
+                 hipSuccess;
+      }
+      if (ok && o == 0 && rows && gnw) {
+        keep.words.resize(gnw);
+        keep.prefix.resize(gnw);
+        ok = hipMemcpyAsync(keep.words.data(), p.scr + p.lay.gwords, 8 * gnw, hipMemcpyDeviceToHost, s) ==
+                 hipSuccess &&
+             hipMemcpyAsync(keep.prefix.data(), p.scr + p.lay.gcnt, 4 * gnw, hipMemcpyDeviceToHost, s) ==
+                 hipSuccess;
+      }
+      if (!ok) rc = fail(e0, NGPU_EHIP, "%s: part %u: gathering the keep bits failed", what, o);
+    }
+  }
+  // Step 3's half that both calls have, after the mid-way wait: the retire
+  // counters of every part (the first words of its pinned block) and their verdict.
+  NodeRetireVerdict verdict() {
+    std::vector<uint64_t> h_ctr((size_t)W * kNodeRetireCtrWords);
+    for (uint32_t o = 0; o < W; ++o)
+      memcpy(&h_ctr[(size_t)o * kNodeRetireCtrWords], node->eng[o]->fold_h, 8 * kNodeRetireCtrWords);
+    const NodeRetireVerdict v = node_retire_verdict(W, h_ctr.data(), m);
+    if (!v.ok())
+      rc = fail(e0, NGPU_EINVAL,
+                "%s: the parts do not tile the dict's ids (%s, part %u; %llu survivors of %llu)", what,
+                v.refusal == kNodeRetireCounter
+                    ? (v.which == kNodeRetireBadGid ? "an id past the dict's entries"
+                       : v.which == kNodeRetireDupBit ? "an id held twice" : "an id held by two parts")
+                    : v.refusal == kNodeRetireSum ? "the parts' survivors do not add up" : "too many survivors",
+                v.bad, (unsigned long long)v.S, (unsigned long long)m);
+    return v;
+  }
+  // Steps 4 and 5 (rc == 0, the remap of nb0 words in every part's scratch, or
+  // ordered before this on its stream): every part's survivors onto a storage of
+  // its own and its table, the node handle's placement rows meanwhile, the last
+  // wait and the handle of n_kept blobs, its blob table base's rows by blob_rows.
+  // ev: the trace events around the compaction are ev and ev + 1; part_line(o, p):
+  // the part's trace line.  Releases everything on every path.
+  template <class Line>
+  int finish(const NodeRetireVerdict &v, uint32_t n_kept, const std::vector<uint32_t> &blob_rows, int ev,
+             Line &&part_line, ngpu_dict **out) {
+    const NodeRetireCaps caps = node_retire_caps(v);
+    const uint64_t S = v.S;
+    for (uint32_t o = 0; o < W && !rc; ++o) {
+      RetirePart &p = pt[o];
+      const ngpu_dict *bp = base->parts[o];
+      DeviceGuard dg(node->dev[o]);
+      if ((rc = storage_alloc(node->eng[o], caps.rec_cap[o], caps.table_cap[o], false, &p.dst))) {
+        rc = fail(e0, rc, "%s", ngpu_last_error(node->eng[o]));
+        break;
+      }
+      p.dst->used = v.s[o];
+      const hipStream_t s = p.bs->s;
+      mark(p, ev);
+      launch_node_dict_compact(bp->st ? bp->st->rec : nullptr, p.m_o, (const uint64_t *)(p.scr + p.lay.words),
+                               (const uint32_t *)(p.scr + p.lay.cnt), (const uint64_t *)(p.scr + p.lay.gwords),
+                               (const uint32_t *)(p.scr + p.lay.gcnt), m, (const uint32_t *)(p.scr + p.lay.remap),
+                               nb0, p.dst->rec, v.s[o], s);
+      launch_dict_build(p.dst->rec, v.s[o], p.dst->table, p.dst->table_cap, s);
+      mark(p, ev + 1);
+      if (hipGetLastError() != hipSuccess)
+        rc = fail(e0, NGPU_EHIP, "%s: part %u: compaction failed", what, o);
+    }
+    stamp(2);
+    // the node handle's placement rows, while the devices move the records
+    DictStorage *hst = nullptr;
+    if (!rc && !(rc = storage_alloc_place_only(e0, rows && S ? caps.place_cap : 0, &hst))) {
+      hst->rec_cap = caps.place_cap;
+      hst->used = S;
+      if (rows && S) dict_retire_place(keep, m, rows, hst->place, S);
+    }
+    quiesce();
+    stamp(3);
+    if (rc) {
+      storage_unref(hst);
+      release();
+      return rc;
+    }
+    if (trace)
+      for (uint32_t o = 0; o < W; ++o) {
+        part_line(o, pt[o]);
+        (void)hipGetLastError();
+      }
+    ngpu_dict *d = dict_derive(base);
+    d->dev.m = S;
+    d->dev.n_blobs = n_kept;
+    d->st = hst;
+    d->has_place = rows && S;
+    for (uint32_t o = 0; o < W; ++o) {
+      ngpu_dict *p = dict_derive(base->parts[o]);
+      p->st = pt[o].dst;
+      pt[o].dst = nullptr;
+      dict_bind(p, v.s[o], n_kept);
+      d->parts.push_back(p);
+    }
+    d->blob_table = dict_retire_blob_table(base->blob_table, blob_rows);
+    release();
+    stamp(4);
+    if (trace)
+      fprintf(stderr,
+              "ngpu %s host W=%u m=%llu enqueue_ms=%.3f wait_ms=%.3f alloc_launch_ms=%.3f "
+              "place_wait_ms=%.3f release_ms=%.3f\n",
+              sym, W, (unsigned long long)m, t_host[0], t_host[1] - t_host[0], t_host[2] - t_host[1],
+              t_host[3] - t_host[2], t_host[4] - t_host[3]);
+    *out = d;
+    return 0;
+  }
+};
+
+// The device time between two of a part's trace events, in microseconds (-1: none).
+double part_us(const RetirePart &p, int a, int b) {
+  float ms = 0;
+  if (!p.t[a] || !p.t[b] || hipEventElapsedTime(&ms, p.t[a], p.t[b]) != hipSuccess) return -1.0;
+  return ms * 1000.0;
+}
+
 int node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t *blobs, uint32_t n,
                            ngpu_dict **out) {
   ngpu_engine *e0 = node->eng[0];
-  const uint32_t W = (uint32_t)node->eng.size();
   if (int rc = node_dict_base_check(node, base, "retire")) return rc;
   if (base->replicated) return node_dict_retire(node, base, blobs, n, out);
   const DictRetirePlan plan = dict_retire_plan(base->dev.n_blobs, blobs, n);
   if (!plan.ok)
     return fail(e0, NGPU_EINVAL, "node dict retire: blob %u of a dict of %u blobs", plan.bad,
                 base->dev.n_blobs);
-  const uint64_t m = base->dev.m, gnw = (m + 63) / 64;
-  const uint32_t nb0 = base->dev.n_blobs;
-  const DictPlace *rows = base->place();
-  const char *tv = getenv("NGPU_DICT_TRACE");
-  const bool trace = tv && tv[0] == '1';
-  // the trace's host side: milliseconds since the call began at the end of each phase
-  const auto t_begin = std::chrono::steady_clock::now();
-  double t_host[5] = {};
-  auto stamp = [&](int i) {
-    if (trace) t_host[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  };
-  std::vector<RetirePart> pt(W);
-  // the engines' kept pinned counter words (fold_h, under fold_mu in index order as
-  // node_dict_fold takes them): a pinned allocation per call costs milliseconds
-  std::vector<std::unique_lock<std::mutex>> lanes;
-  for (uint32_t o = 0; o < W; ++o) lanes.emplace_back(node->eng[o]->fold_mu);
-  for (uint32_t o = 0; o < W; ++o) {
-    ngpu_engine *e = node->eng[o];
-    DeviceGuard dg(e->device);
-    if (!e->fold_h && hipHostMalloc((void **)&e->fold_h, 512) != hipSuccess) {
-      (void)hipGetLastError();
-      e->fold_h = nullptr;
-      return fail(e0, NGPU_ENOMEM, "node dict retire: pinned counters");
-    }
-  }
+  PartsCall c(node, base, "node dict retire", "node_dict_retire_parts");
+  const uint32_t W = c.W;
+  const uint64_t m = c.m, gnw = c.gnw;
+  if (int rc = c.pinned()) return rc;
   static_assert(8 * kNodeRetireCtrWords <= 512, "the counters fit the engines' pinned words");
-  std::vector<uint64_t> h_ctr((size_t)W * kNodeRetireCtrWords);
-  DictKeep keep;
-  int rc = 0;
-  auto quiesce = [&] {  // every stream the call used, whatever another one said
-    for (uint32_t o = 0; o < W; ++o) {
-      if (!pt[o].bs || !pt[o].bs->s) continue;
-      DeviceGuard dg(node->dev[o]);
-      if (hipStreamSynchronize(pt[o].bs->s) != hipSuccess && !rc)
-        rc = fail(e0, NGPU_EHIP, "node dict retire: part %u failed on its device", o);
-    }
-  };
-  auto release = [&] {  // after quiesce(): the scratch, the events, storages not handed over
-    for (uint32_t o = 0; o < W; ++o) {
-      RetirePart &p = pt[o];
-      DeviceGuard dg(node->dev[o]);
-      if (p.scr) (void)hipFree(p.scr);
-      if (p.ready) (void)hipEventDestroy(p.ready);
-      for (hipEvent_t ev : p.t)
-        if (ev) (void)hipEventDestroy(ev);
-      storage_unref(p.dst);
-    }
-  };
-  auto mark = [&](RetirePart &p, int i) {
-    if (trace && p.t[i]) (void)hipEventRecord(p.t[i], p.bs->s);
-  };
 
   // 1. every part's keep words and its bitmap over the global ids
-  for (uint32_t o = 0; o < W && !rc; ++o) {
-    RetirePart &p = pt[o];
+  for (uint32_t o = 0; o < W && !c.rc; ++o) {
     const ngpu_dict *bp = base->parts[o];
     DeviceGuard dg(node->dev[o]);
-    p.m_o = bp->dev.m;
-    p.lay = node_retire_scratch_layout(p.m_o, m, W, plan.bitmap.size(), plan.remap.size());
-    p.bs.reset(new BuildStream(node->dev[o]));
-    if (!p.bs->s || hipEventCreateWithFlags(&p.ready, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: no build stream", o);
+    if (!c.part_begin(o, node_retire_scratch_layout(bp->dev.m, m, W, plan.bitmap.size(), plan.remap.size()),
+                      5))
       break;
-    }
-    for (int i = 0; trace && i < 5; ++i)
-      if (hipEventCreate(&p.t[i]) != hipSuccess) p.t[i] = nullptr;
-    if (hipMalloc((void **)&p.scr, p.lay.bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      p.scr = nullptr;
-      rc = fail(e0, NGPU_ENOMEM, "node dict retire: part %u: scratch allocation failed", o);
-      break;
-    }
+    RetirePart &p = c.pt[o];
     const hipStream_t s = p.bs->s;
     uint64_t *d_ctr = (uint64_t *)(p.scr + p.lay.ctr);
     bool ok = hipMemcpyAsync(p.scr + p.lay.bits, plan.bitmap.data(), 4 * plan.bitmap.size(),
@@ -624,154 +805,197 @@ int node_dict_retire_parts(ngpu_node *node, ngpu_dict *base, const uint32_t *blo
               hipMemsetAsync(d_ctr, 0, 8 * kNodeRetireCtrWords, s) == hipSuccess &&
               (!gnw || hipMemsetAsync(p.scr + p.lay.own, 0, 8 * gnw, s) == hipSuccess);
     if (ok) {
-      mark(p, 0);
+      c.mark(p, 0);
       launch_node_keep_scan(bp->st ? bp->st->rec : nullptr, p.m_o, (const uint32_t *)(p.scr + p.lay.bits),
-                            nb0, m, (uint64_t *)(p.scr + p.lay.words), (uint32_t *)(p.scr + p.lay.cnt),
+                            c.nb0, m, (uint64_t *)(p.scr + p.lay.words), (uint32_t *)(p.scr + p.lay.cnt),
                             (uint64_t *)(p.scr + p.lay.sums), (uint64_t *)(p.scr + p.lay.own), d_ctr, s);
-      mark(p, 1);
+      c.mark(p, 1);
       ok = hipGetLastError() == hipSuccess && hipEventRecord(p.ready, s) == hipSuccess;
     }
-    if (!ok) rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: keep scan failed", o);
+    if (!ok) c.rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: keep scan failed", o);
   }
   // 2. all-gather of the bitmaps, their OR and the global scan, on every part
-  for (uint32_t o = 0; o < W && !rc; ++o) {
-    RetirePart &p = pt[o];
-    DeviceGuard dg(node->dev[o]);
-    const hipStream_t s = p.bs->s;
-    bool ok = true;
-    for (uint32_t q = 0; q < W && ok && gnw; ++q) {
-      uint8_t *to = p.scr + p.lay.gather + 8 * gnw * q;
-      const uint8_t *from = pt[q].scr + pt[q].lay.own;
-      if (q == o)  // written on this very stream
-        ok = hipMemcpyAsync(to, from, 8 * gnw, hipMemcpyDeviceToDevice, s) == hipSuccess;
-      else
-        ok = hipStreamWaitEvent(s, pt[q].ready, 0) == hipSuccess &&
-             hipMemcpyPeerAsync(to, node->dev[o], from, node->dev[q], 8 * gnw, s) == hipSuccess;
-    }
-    if (ok) {
-      uint64_t *d_ctr = (uint64_t *)(p.scr + p.lay.ctr);
-      launch_node_keep_merge((const uint64_t *)(p.scr + p.lay.gather), W, m,
-                             (uint64_t *)(p.scr + p.lay.gwords), (uint32_t *)(p.scr + p.lay.gcnt),
-                             (uint64_t *)(p.scr + p.lay.gsums),
-                             (const uint64_t *)(p.scr + p.lay.sums) + dict_retire_scan_tiles(p.m_o), d_ctr,
-                             s);
-      mark(p, 2);
-      ok = hipGetLastError() == hipSuccess &&
-           hipMemcpyAsync(node->eng[o]->fold_h, d_ctr, 8 * kNodeRetireCtrWords, hipMemcpyDeviceToHost,
-                          s) == hipSuccess;
-    }
-    if (ok && o == 0 && rows && gnw) {
-      keep.words.resize(gnw);
-      keep.prefix.resize(gnw);
-      ok = hipMemcpyAsync(keep.words.data(), p.scr + p.lay.gwords, 8 * gnw, hipMemcpyDeviceToHost, s) ==
-               hipSuccess &&
-           hipMemcpyAsync(keep.prefix.data(), p.scr + p.lay.gcnt, 4 * gnw, hipMemcpyDeviceToHost, s) ==
-               hipSuccess;
-    }
-    if (!ok) rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: gathering the keep bits failed", o);
+  c.gather_merge(kNodeRetireCtrWords, 2);
+  c.stamp(0);
+  c.quiesce();  // the call's only mid-way wait
+  c.stamp(1);
+  if (c.rc) {
+    c.release();
+    return c.rc;
   }
-  stamp(0);
-  quiesce();  // the call's only mid-way wait
-  stamp(1);
-  if (rc) {
-    release();
-    return rc;
-  }
-
   // 3. the verdict; nothing is allocated before it
-  for (uint32_t o = 0; o < W; ++o)
-    memcpy(&h_ctr[(size_t)o * kNodeRetireCtrWords], node->eng[o]->fold_h, 8 * kNodeRetireCtrWords);
-  const NodeRetireVerdict v = node_retire_verdict(W, h_ctr.data(), m);
-  if (!v.ok()) {
-    rc = fail(e0, NGPU_EINVAL,
-              "node dict retire: the parts do not tile the dict's ids (%s, part %u; %llu survivors of %llu)",
-              v.refusal == kNodeRetireCounter
-                  ? (v.which == kNodeRetireBadGid ? "an id past the dict's entries"
-                     : v.which == kNodeRetireDupBit ? "an id held twice" : "an id held by two parts")
-                  : v.refusal == kNodeRetireSum ? "the parts' survivors do not add up" : "too many survivors",
-              v.bad, (unsigned long long)v.S, (unsigned long long)m);
-    release();
-    return rc;
+  const NodeRetireVerdict v = c.verdict();
+  if (c.rc) {
+    c.release();
+    return c.rc;
   }
-  const NodeRetireCaps caps = node_retire_caps(v);
-  const uint64_t S = v.S;
+  // 4. and 5.
+  return c.finish(v, plan.n_kept, plan.remap, 3,
+                  [&](uint32_t o, const RetirePart &p) {
+                    const double a = part_us(p, 0, 1), b = part_us(p, 1, 2), k = part_us(p, 3, 4);
+                    if (a >= 0 && b >= 0 && k >= 0)
+                      fprintf(stderr,
+                              "ngpu node_dict_retire_parts part=%u m=%llu m_o=%llu s_o=%llu device_us=%.1f "
+                              "keep_scan_us=%.1f gather_merge_us=%.1f compact_build_us=%.1f\n",
+                              o, (unsigned long long)m, (unsigned long long)p.m_o, (unsigned long long)v.s[o],
+                              a + b + k, a, b, k);
+                  },
+                  out);
+}
 
-  // 4. every part's survivors onto a storage of its own, and its table
-  for (uint32_t o = 0; o < W && !rc; ++o) {
-    RetirePart &p = pt[o];
+// ---- node dict distill across parts --------------------------------------------
+// ngpu_node_dict_distill_parts: the distill of a partitioned dict.  All rows of a
+// digest live on one part and a part's rows are in ascending gid order, so a part
+// counts its own rows through its own table and its winners are the dict's; the
+// survivors' new global ids and the live blobs are over all parts.  The steps are
+// those of node_dict_retire_parts above, with these differences:
+//   1. refs, the counters (a retire's and distill's 35, side by side), the live
+//      words and the part's bitmap are zeroed; launch_dict_ref_count, then
+//      launch_node_distill_keep_scan (node_distill.hip): distill's keep pass and
+//      the retire's in one.
+//   2. the same exchange; the one copy of counters brings both blocks back, a
+//      second the part's live bitmap (to memory of the call's own).
+//   3. the verdict, then node_distill_sum (node_distill_plan.hpp): every part's
+//      counters against its m_o and s_o, their sums, the OR of the live bitmaps;
+//      distill_blob_plan over the union; the remap goes up to every part.  A
+//      count-only call ends here.
+//   4. and 5. unchanged.
+int node_dict_distill_parts(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                            ngpu_dict **out, ngpu_dict_distill_info *info) {
+  ngpu_engine *e0 = node->eng[0];
+  if (int rc = node_dict_base_check(node, base, "distill")) return rc;
+  if ((flags & NGPU_DICT_DISTILL_MERGE_BLOB_IDS) && base->dev.m && base->blob_table.empty())
+    return fail(e0, NGPU_EINVAL,
+                "node dict distill: blob ids are merged by the blob table, the dict has none");
+  if (base->replicated) return node_dict_distill(node, base, min_refs, flags, out, info);
+  if (base->dev.n_blobs > kDictMaxBlobs)
+    return fail(e0, NGPU_EINVAL, "node dict distill: a dict of %u blobs", base->dev.n_blobs);
+  PartsCall c(node, base, "node dict distill", "node_dict_distill_parts");
+  const uint32_t W = c.W, nb0 = c.nb0;
+  const uint64_t m = c.m, gnw = c.gnw, lw = distill_live_words(nb0);
+  std::vector<uint64_t> m_o(W);
+  uint64_t total = 0;
+  for (uint32_t o = 0; o < W; ++o) total += m_o[o] = base->parts[o]->dev.m;
+  if (total != m)
+    return fail(e0, NGPU_EINVAL, "node dict distill: the parts hold %llu rows, the dict %llu entries",
+                (unsigned long long)total, (unsigned long long)m);
+  if (int rc = c.pinned()) return rc;
+  static_assert(8 * kNodeDistillBackWords <= 512, "the counters fit the engines' pinned words");
+  std::vector<uint32_t> h_live((size_t)W * lw, 0);
+  std::vector<NodeDistillScratch> lay(W);
+
+  // 1. every part's counts, keep words and its bitmap over the global ids
+  for (uint32_t o = 0; o < W && !c.rc; ++o) {
     const ngpu_dict *bp = base->parts[o];
     DeviceGuard dg(node->dev[o]);
-    if ((rc = storage_alloc(node->eng[o], caps.rec_cap[o], caps.table_cap[o], false, &p.dst))) {
-      rc = fail(e0, rc, "%s", ngpu_last_error(node->eng[o]));
-      break;
-    }
-    p.dst->used = v.s[o];
+    lay[o] = node_distill_scratch_layout(m_o[o], m, W, nb0);
+    if (!c.part_begin(o, lay[o].r, 6)) break;
+    RetirePart &p = c.pt[o];
     const hipStream_t s = p.bs->s;
-    mark(p, 3);
-    launch_node_dict_compact(bp->st ? bp->st->rec : nullptr, p.m_o, (const uint64_t *)(p.scr + p.lay.words),
-                             (const uint32_t *)(p.scr + p.lay.cnt), (const uint64_t *)(p.scr + p.lay.gwords),
-                             (const uint32_t *)(p.scr + p.lay.gcnt), m, (const uint32_t *)(p.scr + p.lay.remap),
-                             nb0, p.dst->rec, v.s[o], s);
-    launch_dict_build(p.dst->rec, v.s[o], p.dst->table, p.dst->table_cap, s);
-    mark(p, 4);
-    if (hipGetLastError() != hipSuccess)
-      rc = fail(e0, NGPU_EHIP, "node dict retire: part %u: compaction failed", o);
-  }
-  stamp(2);
-  // the node handle's placement rows, while the devices move the records
-  DictStorage *hst = nullptr;
-  if (!rc && !(rc = storage_alloc_place_only(e0, rows && S ? caps.place_cap : 0, &hst))) {
-    hst->rec_cap = caps.place_cap;
-    hst->used = S;
-    if (rows && S) dict_retire_place(keep, m, rows, hst->place, S);
-  }
-  quiesce();
-  stamp(3);
-  if (rc) {
-    storage_unref(hst);
-    release();
-    return rc;
-  }
-  if (trace)
-    for (uint32_t o = 0; o < W; ++o) {
-      float a = 0, b = 0, c = 0;
-      const RetirePart &p = pt[o];
-      if (p.t[0] && p.t[1] && p.t[2] && p.t[3] && p.t[4] &&
-          hipEventElapsedTime(&a, p.t[0], p.t[1]) == hipSuccess &&
-          hipEventElapsedTime(&b, p.t[1], p.t[2]) == hipSuccess &&
-          hipEventElapsedTime(&c, p.t[3], p.t[4]) == hipSuccess)
-        fprintf(stderr,
-                "ngpu node_dict_retire_parts part=%u m=%llu m_o=%llu s_o=%llu device_us=%.1f keep_scan_us=%.1f "
-                "gather_merge_us=%.1f compact_build_us=%.1f\n",
-                o, (unsigned long long)m, (unsigned long long)p.m_o, (unsigned long long)v.s[o],
-                (a + b + c) * 1000.0, a * 1000.0, b * 1000.0, c * 1000.0);
-      (void)hipGetLastError();
+    uint64_t *d_ctr = (uint64_t *)(p.scr + p.lay.ctr);
+    uint32_t *d_refs = (uint32_t *)(p.scr + lay[o].refs);
+    const DictRec *rec = bp->st ? bp->st->rec : nullptr;
+    bool ok = hipMemsetAsync(d_ctr, 0, 8 * kNodeDistillBackWords, s) == hipSuccess &&
+              hipMemsetAsync(p.scr + lay[o].live, 0, lay[o].zero_bytes, s) == hipSuccess &&
+              (!gnw || hipMemsetAsync(p.scr + p.lay.own, 0, 8 * gnw, s) == hipSuccess);
+    if (ok) {
+      c.mark(p, 0);
+      launch_dict_ref_count(rec, p.m_o, bp->st ? bp->st->table : nullptr, bp->st ? bp->st->table_cap : 0,
+                            d_refs, s);
+      c.mark(p, 1);
+      launch_node_distill_keep_scan(rec, p.m_o, d_refs, min_refs, nb0, m, (uint64_t *)(p.scr + p.lay.words),
+                                    (uint32_t *)(p.scr + p.lay.cnt), (uint64_t *)(p.scr + p.lay.sums),
+                                    (uint32_t *)(p.scr + lay[o].live), (uint64_t *)(p.scr + lay[o].stats),
+                                    (uint64_t *)(p.scr + p.lay.own), d_ctr, s);
+      c.mark(p, 2);
+      ok = hipGetLastError() == hipSuccess && hipEventRecord(p.ready, s) == hipSuccess;
     }
-
-  // 5. the handle
-  ngpu_dict *d = dict_derive(base);
-  d->dev.m = S;
-  d->dev.n_blobs = plan.n_kept;
-  d->st = hst;
-  d->has_place = rows && S;
-  for (uint32_t o = 0; o < W; ++o) {
-    ngpu_dict *p = dict_derive(base->parts[o]);
-    p->st = pt[o].dst;
-    pt[o].dst = nullptr;
-    dict_bind(p, v.s[o], plan.n_kept);
-    d->parts.push_back(p);
+    if (!ok) c.rc = fail(e0, NGPU_EHIP, "node dict distill: part %u: counting failed", o);
   }
-  d->blob_table = dict_retire_blob_table(base->blob_table, plan.remap);
-  release();
-  stamp(4);
-  if (trace)
-    fprintf(stderr,
-            "ngpu node_dict_retire_parts host W=%u m=%llu enqueue_ms=%.3f wait_ms=%.3f alloc_launch_ms=%.3f "
-            "place_wait_ms=%.3f release_ms=%.3f\n",
-            W, (unsigned long long)m, t_host[0], t_host[1] - t_host[0], t_host[2] - t_host[1],
-            t_host[3] - t_host[2], t_host[4] - t_host[3]);
-  *out = d;
-  return 0;
+  // 2. all-gather of the bitmaps, their OR and the global scan, on every part;
+  //    the counters and the live blobs come back
+  c.gather_merge(kNodeDistillBackWords, 3);
+  for (uint32_t o = 0; o < W && !c.rc; ++o) {
+    DeviceGuard dg(node->dev[o]);
+    if (hipMemcpyAsync(&h_live[(size_t)o * lw], c.pt[o].scr + lay[o].live, 4 * lw, hipMemcpyDeviceToHost,
+                       c.pt[o].bs->s) != hipSuccess)
+      c.rc = fail(e0, NGPU_EHIP, "node dict distill: part %u: the live blobs did not come back", o);
+  }
+  c.stamp(0);
+  c.quiesce();  // the call's only mid-way wait
+  c.stamp(1);
+  if (c.rc) {
+    c.release();
+    return c.rc;
+  }
+  // 3. the verdict, the counters of the whole dict and what becomes of the blobs;
+  //    nothing is allocated before it
+  const NodeRetireVerdict v = c.verdict();
+  if (c.rc) {
+    c.release();
+    return c.rc;
+  }
+  std::vector<uint64_t> h_back((size_t)W * kNodeDistillBackWords);
+  for (uint32_t o = 0; o < W; ++o)
+    memcpy(&h_back[(size_t)o * kNodeDistillBackWords], node->eng[o]->fold_h, 8 * kNodeDistillBackWords);
+  const NodeDistillSum sum = node_distill_sum(W, h_back.data(), h_live.data(), nb0, m_o.data(), v.s.data());
+  if (!sum.ok(W)) {
+    const uint64_t *st = &h_back[(size_t)sum.bad_part * kNodeDistillBackWords + kNodeRetireCtrWords];
+    c.rc = fail(e0, NGPU_EHIP, "node dict distill: part %u: %llu survivors, %llu digests of %llu records",
+                sum.bad_part, (unsigned long long)v.s[sum.bad_part], (unsigned long long)st[kDistillDistinct],
+                (unsigned long long)m_o[sum.bad_part]);
+    c.release();
+    return c.rc;
+  }
+  const DistillBlobPlan plan = distill_blob_plan(
+      nb0, sum.live.data(), flags,
+      base->blob_table.size() >= 256ull * nb0 && nb0 ? base->blob_table.data() : nullptr);
+  if (!plan.ok) {
+    c.rc = fail(e0, NGPU_EINVAL, "node dict distill: a dict of %u blobs", nb0);
+    c.release();
+    return c.rc;
+  }
+  if (info) distill_info_fill(info, m, sum.stats, nb0, plan.n_kept);
+  if (!out) {  // a count
+    if (c.trace)
+      for (uint32_t o = 0; o < W; ++o) {
+        const RetirePart &p = c.pt[o];
+        const double a = part_us(p, 0, 1), b = part_us(p, 1, 2), g = part_us(p, 2, 3);
+        if (a >= 0 && b >= 0 && g >= 0)
+          fprintf(stderr,
+                  "ngpu node_dict_distill_parts part=%u m=%llu m_o=%llu s_o=%llu device_us=%.1f count_us=%.1f "
+                  "keep_scan_us=%.1f gather_merge_us=%.1f compact_build_us=%.1f\n",
+                  o, (unsigned long long)m, (unsigned long long)p.m_o, (unsigned long long)v.s[o], a + b + g, a,
+                  b, g, 0.0);
+        (void)hipGetLastError();
+      }
+    c.release();
+    return 0;
+  }
+  for (uint32_t o = 0; o < W && !c.rc && nb0; ++o) {
+    DeviceGuard dg(node->dev[o]);
+    if (hipMemcpyAsync(c.pt[o].scr + c.pt[o].lay.remap, plan.remap.data(), 4ull * nb0, hipMemcpyHostToDevice,
+                       c.pt[o].bs->s) != hipSuccess)
+      c.rc = fail(e0, NGPU_EHIP, "node dict distill: part %u: upload failed", o);
+  }
+  if (c.rc) {
+    c.quiesce();
+    c.release();
+    return c.rc;
+  }
+  // 4. and 5.
+  return c.finish(v, plan.n_kept, plan.rows, 4,
+                  [&](uint32_t o, const RetirePart &p) {
+                    const double a = part_us(p, 0, 1), b = part_us(p, 1, 2), g = part_us(p, 2, 3),
+                                 k = part_us(p, 4, 5);
+                    if (a >= 0 && b >= 0 && g >= 0 && k >= 0)
+                      fprintf(stderr,
+                              "ngpu node_dict_distill_parts part=%u m=%llu m_o=%llu s_o=%llu device_us=%.1f "
+                              "count_us=%.1f keep_scan_us=%.1f gather_merge_us=%.1f compact_build_us=%.1f\n",
+                              o, (unsigned long long)m, (unsigned long long)p.m_o, (unsigned long long)v.s[o],
+                              a + b + g + k, a, b, g, k);
+                  },
+                  out);
 }
 
 // ngpu_node_dict_export of a partitioned dict: every part's HBM rows come back in
@@ -1492,6 +1716,20 @@ int ngpu_node_dict_distill(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, 
     ngpu_dict_distill_info got;
     memset(&got, 0, sizeof got);
     const int rc = node_dict_distill(node, base, min_refs, flags, out, &got);
+    if (!rc && info) *info = got;
+    return rc;
+  });
+}
+
+int ngpu_node_dict_distill_parts(ngpu_node *node, ngpu_dict *base, uint32_t min_refs, uint32_t flags,
+                                 ngpu_dict **out, ngpu_dict_distill_info *info) {
+  if (out) *out = nullptr;
+  if (info) memset(info, 0, sizeof *info);
+  if (!base || !node || dict_distill_args(flags)) return NGPU_EINVAL;
+  return guarded([&]() -> int {
+    ngpu_dict_distill_info got;
+    memset(&got, 0, sizeof got);
+    const int rc = node_dict_distill_parts(node, base, min_refs, flags, out, &got);
     if (!rc && info) *info = got;
     return rc;
   });

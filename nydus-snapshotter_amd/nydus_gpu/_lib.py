@@ -96,7 +96,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # dict save (additive in ABI 7)
            "ngpu_dict_save_layout", "ngpu_dict_save", "ngpu_node_dict_save",
            # dict distill (additive in ABI 7)
-           "ngpu_dict_distill", "ngpu_node_dict_distill"]
+           "ngpu_dict_distill", "ngpu_node_dict_distill",
+           # node dict distill across parts (additive in ABI 7)
+           "ngpu_node_dict_distill_parts"]
 
 # ngpu_dict_place: the compressed placement of one folded record (host rows)
 DICT_PLACE_DTYPE = np.dtype([("compressed_offset", "<u8"), ("compressed_size", "<u4"), ("flags", "<u4")])
@@ -401,6 +403,8 @@ def lib():
     L.ngpu_node_dict_export.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, u32, ctypes.POINTER(u32), u32]
     L.ngpu_dict_distill.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(NgpuDictDistillInfo)]
     L.ngpu_node_dict_distill.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(NgpuDictDistillInfo)]
+    L.ngpu_node_dict_distill_parts.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp),
+                                               ctypes.POINTER(NgpuDictDistillInfo)]
     L.ngpu_dict_save_layout.argtypes = [u64, u32, ctypes.POINTER(NgpuDictSaveInfo)]
     L.ngpu_dict_save.argtypes = [vp, vp, ctypes.POINTER(NgpuDictSaveOptions), WRITE_FN, vp,
                                  ctypes.POINTER(NgpuDictSaveInfo)]
@@ -1714,6 +1718,15 @@ class Node:
         a partitioned one raises NgpuError (EUNSUPP)."""
         h, info = _dict_distill(lambda *a: lib().ngpu_node_dict_distill(self._h, base._h, *a), self._err,
                                 "node_dict_distill", min_refs, keep_blobs, merge_blob_ids, count_only)
+        return (None if h is None else ChunkDict(h)), info
+
+    def dict_distill_parts(self, base: ChunkDict, min_refs: int = 1, *, keep_blobs: bool = False,
+                           merge_blob_ids: bool = False, count_only: bool = False):
+        """ngpu_node_dict_distill_parts: dict_distill for node dicts of either mode;
+        a partitioned dict's parts count their own rows on their devices, and the
+        survivors are re-numbered and the live blobs decided across all of them."""
+        h, info = _dict_distill(lambda *a: lib().ngpu_node_dict_distill_parts(self._h, base._h, *a), self._err,
+                                "node_dict_distill_parts", min_refs, keep_blobs, merge_blob_ids, count_only)
         return (None if h is None else ChunkDict(h)), info
 
     def dict_export_parts(self, d: ChunkDict):
