@@ -30,7 +30,8 @@ constexpr Sched kSched = make_sched();
 // The VALU issue order is fixed by hand (inline asm, one op per statement;
 // volatile statements keep their order): the 4 independent G of a column /
 // diagonal step advance in lockstep, so the 2-cycle ops (v_xor, v_add) issue
-// in runs of 4 and 8 between runs of 4-cycle ops (v_add3, v_alignbit).  The
+// in runs of 4 and 8 between runs of 4-cycle ops (v_add3, v_alignbit), and
+// the wave's priority follows the runs (B3_PRIO below).  The
 // compiler's own schedule of the same G macro alternates them one by one and
 // is 6 % slower on the box (5.89 -> 5.52 ms per 16 GiB C2 launch,
 // profiles/r1/ab_issue_order.jsonl); SDWA rotr16 and split v_add3 were
@@ -43,29 +44,62 @@ constexpr Sched kSched = make_sched();
 #define B3_OP3(op, a, b, x) asm volatile(op " %0, %0, %1, %2" : "+v"(a) : "v"(b), "v"(x))
 #define B3_OP2(op, a, b) asm volatile(op " %0, %0, %1" : "+v"(a) : "v"(b))
 #define B3_ROT(a, n) asm volatile("v_alignbit_b32 %0, %0, %0, " #n : "+v"(a))
+// Wave priority by run (B3_PRIO 1; 0 is the stream without it, kept for the
+// A/B like B3_LOAD128): priority 1 on the runs of 4-cycle ops (a step's last
+// rotates and the next step's add3 make one run of 8), 0 on the runs of
+// 2-cycle ops.  VALU issue between a SIMD's waves goes by priority, then age:
+// at equal priority the oldest wave issues back to back, the others sit one
+// run behind it and a 2-cycle op never meets another wave's 2-cycle op, so
+// every instruction costs ~4 cycles.  With the flips the SIMD drains every
+// wave's slow run first, and the waves left in fast runs at equal priority
+// alternate at 2 cycles per instruction: 3.82 -> 2.58 cycles per instruction
+// at 4 waves per SIMD in tools/valu_bank.hip, 40.4 -> 56.8 T in
+// tools/b3_ceiling.hip (profiles/r9/valu_prio_screen.json; the inverse order
+// and flips at the runs of 8 only were measured there and lose).
+// s_setprio ignores EXEC and compress() runs inside divergent code (finish()'s
+// merge loop, b3_tree's comp branches), so compress() is one straight line
+// from its first raise to the drop at its end: no branch in between.
+#ifndef B3_PRIO
+#define B3_PRIO 1
+#endif
+#if B3_PRIO
+#define B3_PRIO_SLOW asm volatile("s_setprio 1")
+#define B3_PRIO_FAST asm volatile("s_setprio 0")
+#else
+#define B3_PRIO_SLOW (void)0
+#define B3_PRIO_FAST (void)0
+#endif
 // One column or diagonal step (4 G in lockstep).
 #define B3_G4(a0, b0, c0, d0, a1, b1, c1, d1, a2, b2, c2, d2, a3, b3, c3, d3, x0, x1, x2, x3, \
               y0, y1, y2, y3)                                                               \
   do {                                                                                      \
     B3_OP3("v_add3_u32", a0, b0, x0); B3_OP3("v_add3_u32", a1, b1, x1);                    \
     B3_OP3("v_add3_u32", a2, b2, x2); B3_OP3("v_add3_u32", a3, b3, x3);                    \
+    B3_PRIO_FAST;                                                                           \
     B3_OP2("v_xor_b32", d0, a0); B3_OP2("v_xor_b32", d1, a1);                              \
     B3_OP2("v_xor_b32", d2, a2); B3_OP2("v_xor_b32", d3, a3);                              \
+    B3_PRIO_SLOW;                                                                           \
     B3_ROT(d0, 16); B3_ROT(d1, 16); B3_ROT(d2, 16); B3_ROT(d3, 16);                         \
+    B3_PRIO_FAST;                                                                           \
     B3_OP2("v_add_u32", c0, d0); B3_OP2("v_add_u32", c1, d1);                              \
     B3_OP2("v_add_u32", c2, d2); B3_OP2("v_add_u32", c3, d3);                              \
     B3_OP2("v_xor_b32", b0, c0); B3_OP2("v_xor_b32", b1, c1);                              \
     B3_OP2("v_xor_b32", b2, c2); B3_OP2("v_xor_b32", b3, c3);                              \
+    B3_PRIO_SLOW;                                                                           \
     B3_ROT(b0, 12); B3_ROT(b1, 12); B3_ROT(b2, 12); B3_ROT(b3, 12);                         \
     B3_OP3("v_add3_u32", a0, b0, y0); B3_OP3("v_add3_u32", a1, b1, y1);                    \
     B3_OP3("v_add3_u32", a2, b2, y2); B3_OP3("v_add3_u32", a3, b3, y3);                    \
+    B3_PRIO_FAST;                                                                           \
     B3_OP2("v_xor_b32", d0, a0); B3_OP2("v_xor_b32", d1, a1);                              \
     B3_OP2("v_xor_b32", d2, a2); B3_OP2("v_xor_b32", d3, a3);                              \
+    B3_PRIO_SLOW;                                                                           \
     B3_ROT(d0, 8); B3_ROT(d1, 8); B3_ROT(d2, 8); B3_ROT(d3, 8);                             \
+    B3_PRIO_FAST;                                                                           \
     B3_OP2("v_add_u32", c0, d0); B3_OP2("v_add_u32", c1, d1);                              \
     B3_OP2("v_add_u32", c2, d2); B3_OP2("v_add_u32", c3, d3);                              \
     B3_OP2("v_xor_b32", b0, c0); B3_OP2("v_xor_b32", b1, c1);                              \
     B3_OP2("v_xor_b32", b2, c2); B3_OP2("v_xor_b32", b3, c3);                              \
+    B3_PRIO_SLOW;                                                                           \
     B3_ROT(b0, 7); B3_ROT(b1, 7); B3_ROT(b2, 7); B3_ROT(b3, 7);                             \
   } while (0)
 
@@ -80,24 +114,32 @@ constexpr Sched kSched = make_sched();
   do {                                                                                  \
     B3_OP3("v_add3_u32", v0, v4, x0); B3_OP3("v_add3_u32", v1, v5, x1);                \
     B3_OP3("v_add3_u32", v2, v6, x2); B3_OP3("v_add3_u32", v3, v7, x3);                \
+    B3_PRIO_FAST;                                                                       \
     B3_XORTO(v12, counter, v0); B3_XORTO(v14, blen, v2); B3_XORTO(v15, flags, v3);     \
+    B3_PRIO_SLOW;                                                                       \
     B3_ROT(v12, 16);                                                                    \
     asm volatile("v_alignbit_b32 %0, %1, %1, 16" : "=v"(v13) : "v"(v1));                \
     B3_ROT(v14, 16); B3_ROT(v15, 16);                                                   \
+    B3_PRIO_FAST;                                                                       \
     B3_ADDLIT(v8, IV0, v12); B3_ADDLIT(v9, IV1, v13);                                   \
     B3_ADDLIT(v10, IV2, v14); B3_ADDLIT(v11, IV3, v15);                                 \
     B3_OP2("v_xor_b32", v4, v8); B3_OP2("v_xor_b32", v5, v9);                           \
     B3_OP2("v_xor_b32", v6, v10); B3_OP2("v_xor_b32", v7, v11);                         \
+    B3_PRIO_SLOW;                                                                       \
     B3_ROT(v4, 12); B3_ROT(v5, 12); B3_ROT(v6, 12); B3_ROT(v7, 12);                     \
     B3_OP3("v_add3_u32", v0, v4, y0); B3_OP3("v_add3_u32", v1, v5, y1);                \
     B3_OP3("v_add3_u32", v2, v6, y2); B3_OP3("v_add3_u32", v3, v7, y3);                \
+    B3_PRIO_FAST;                                                                       \
     B3_OP2("v_xor_b32", v12, v0); B3_OP2("v_xor_b32", v13, v1);                         \
     B3_OP2("v_xor_b32", v14, v2); B3_OP2("v_xor_b32", v15, v3);                         \
+    B3_PRIO_SLOW;                                                                       \
     B3_ROT(v12, 8); B3_ROT(v13, 8); B3_ROT(v14, 8); B3_ROT(v15, 8);                     \
+    B3_PRIO_FAST;                                                                       \
     B3_OP2("v_add_u32", v8, v12); B3_OP2("v_add_u32", v9, v13);                         \
     B3_OP2("v_add_u32", v10, v14); B3_OP2("v_add_u32", v11, v15);                       \
     B3_OP2("v_xor_b32", v4, v8); B3_OP2("v_xor_b32", v5, v9);                           \
     B3_OP2("v_xor_b32", v6, v10); B3_OP2("v_xor_b32", v7, v11);                         \
+    B3_PRIO_SLOW;                                                                       \
     B3_ROT(v4, 7); B3_ROT(v5, 7); B3_ROT(v6, 7); B3_ROT(v7, 7);                         \
   } while (0)
 
@@ -115,6 +157,7 @@ __device__ __forceinline__ void compress(uint32_t cv[8], const uint32_t m[16],
                                          uint32_t counter, uint32_t blen, uint32_t flags) {
   uint32_t v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3];
   uint32_t v4 = cv[4], v5 = cv[5], v6 = cv[6], v7 = cv[7];
+  B3_PRIO_SLOW;
 #if B3_FOLD
   uint32_t v8, v9, v10, v11, v12, v13, v14, v15;
   {
@@ -137,6 +180,7 @@ __device__ __forceinline__ void compress(uint32_t cv[8], const uint32_t m[16],
     B3_G4(v0, v5, v10, v15, v1, v6, v11, v12, v2, v7, v8, v13, v3, v4, v9, v14,
           m[s[8]], m[s[10]], m[s[12]], m[s[14]], m[s[9]], m[s[11]], m[s[13]], m[s[15]]);
   }
+  B3_PRIO_FAST;
   cv[0] = v0 ^ v8;  cv[1] = v1 ^ v9;  cv[2] = v2 ^ v10; cv[3] = v3 ^ v11;
   cv[4] = v4 ^ v12; cv[5] = v5 ^ v13; cv[6] = v6 ^ v14; cv[7] = v7 ^ v15;
 }

@@ -8,7 +8,8 @@ Every variant is ONE inline-asm block per loop trip with physical VGPRs
 (clobbered, so the compiler keeps its own values elsewhere); s_memtime
 (shader clock) brackets the loop in every wave.  Bank of vN = N mod 4.
 usage: tools/gen_valu_bank.py [blake3.s]  (the .s: the product kernel's
-hot loop, replayed verbatim as variant `compiled`)"""
+hot loop, replayed verbatim as variant `compiled`; from a -DB3_PRIO=0 build,
+the compiled_raw_prio_* variants place their own s_setprio)"""
 import os
 import re
 import sys
@@ -119,7 +120,49 @@ def streams(compiled_s=None):
                 if (i + 1) % k == 0:
                     ops.append("s_barrier")
             v[f"compiled_bar{k}"] = ops
+        # wave priority steering of compiled_raw (VALU issue between a SIMD's
+        # waves goes by priority, then age): does a wave that raises its
+        # priority for one class of runs let the others' 2-cycle runs pair?
+        raw = v["compiled_raw"]
+        v["compiled_raw_prio_a"] = prio_flips(raw, slow=1, fast=0)   # 1 on 4-cycle runs
+        v["compiled_raw_prio_b"] = prio_flips(raw, slow=0, fast=1)   # the inverse
+        v["compiled_raw_prio_c"] = prio_flips(raw, slow=1, fast=0, min_run=8)  # 8-long runs only
+        # no flips: every other wave of a SIMD at priority 1 for the whole loop
+        v["compiled_raw_prio_static"] = list(raw)
     return v
+
+
+STATIC_PRIO = ("compiled_raw_prio_static",)
+SLOW_OPS = ("v_add3_u32", "v_alignbit_b32")  # the 4-cycle class
+
+
+def prio_flips(ops, slow, fast, min_run=1):
+    """`ops` with an s_setprio in front of every run of one issue class (pads
+    belong to the run they sit in): `slow` before the 4-cycle runs, `fast`
+    before the 2-cycle ones; only runs of at least `min_run` ops flip, the
+    shorter ones keep the priority they inherit.  The trip ends at 0."""
+    valu = [(j, o.startswith(SLOW_OPS)) for j, o in enumerate(ops) if o.startswith("v_")]
+    runs = []  # [first op index, is_slow, length]
+    for j, s in valu:
+        if runs and runs[-1][1] == s:
+            runs[-1][2] += 1
+        else:
+            runs.append([j, s, 1])
+    # the stream loops: its last run continues into its first one
+    wrap = runs[0][2] if runs[0][1] == runs[-1][1] else 0
+    at, cur = {}, 0
+    for k, (j, s, n) in enumerate(runs):
+        want = slow if s else fast
+        if n + (wrap if k in (0, len(runs) - 1) else 0) >= min_run and want != cur:
+            at[j] = cur = want
+    out = []
+    for j, o in enumerate(ops):
+        if j in at:
+            out.append(f"s_setprio {at[j]}")
+        out.append(o)
+    if cur:
+        out.append("s_setprio 0")
+    return out
 
 
 def compiled_stream(path, keep_nops=False):
@@ -164,14 +207,30 @@ def main():
     vs = streams(sys.argv[1] if len(sys.argv) > 1 else None)
     out = ["// GENERATED by tools/gen_valu_bank.py -- see its docstring.",
            "#include <hip/hip_runtime.h>", "#include <stdint.h>", "#include <stdio.h>",
-           "#include <stdlib.h>", "#include <string.h>", ""]
+           "#include <stdlib.h>", "#include <string.h>", "",
+           "// arrival tickets per SIMD (key: XCC_ID | HW_ID's se/sh/cu/pipe/simd bits), zeroed before",
+           "// every launch; only the static-priority variants take one",
+           "__device__ uint32_t g_ticket[1 << 16];", ""]
     names = []
     for name, ops in vs.items():
         rs = regs(ops)
         clob = ", ".join(f'"v{r}"' for r in rs)
         body = "\\n\\t".join(ops)
         out += [f"__global__ __launch_bounds__(1024) void k_{name}(uint64_t *rec, uint32_t iters) {{",
-                "  uint64_t t0, t1;",
+                "  uint64_t t0, t1;"]
+        if name in STATIC_PRIO:
+            # every other wave of a SIMD, by the order they arrive on it (a
+            # ticket per SIMD keyed by HW_ID, no dispatch order assumed); the
+            # guard is an SGPR so only that wave runs the s_setprio
+            out += ["  uint32_t ticket = 0;",
+                    "  if ((threadIdx.x & 63) == 0) {",
+                    "    const uint32_t key = (__builtin_amdgcn_s_getreg(0x7814) & 0xF) << 12 |",
+                    "                         ((__builtin_amdgcn_s_getreg(0xF804) >> 4) & 0xFFF);",
+                    "    ticket = atomicAdd(&g_ticket[key], 1u);",
+                    "  }",
+                    "  if (__builtin_amdgcn_readfirstlane(ticket) & 1)",
+                    '    asm volatile("s_setprio 1");']
+        out += [
                 '  asm volatile("s_memtime %0\\n\\ts_waitcnt lgkmcnt(0)" : "=s"(t0) :: "memory");',
                 "  for (uint32_t it = 0; it < iters; ++it)",
                 f'    asm volatile("{body}" ::: {clob});',
@@ -205,8 +264,13 @@ static void run(const V &v, int w, int threads, int rounds, uint64_t *d, uint64_
   const int waves_total = simds * w * rounds;
   const int blocks = waves_total / (threads / 64);
   const uint32_t iters = (uint32_t)((v.ops > 300 ? 400 : 1000) / rounds);
-  hipLaunchKernelGGL(v.k, dim3(blocks), dim3(threads), 0, 0, d, iters);  // warm / clock ramp
-  hipLaunchKernelGGL(v.k, dim3(blocks), dim3(threads), 0, 0, d, iters);
+  void *tk;
+  if (hipGetSymbolAddress(&tk, HIP_SYMBOL(g_ticket)) != hipSuccess) exit(3);
+  for (int warm = 0; warm < 2; ++warm) {  // warm / clock ramp
+    (void)hipMemsetAsync(tk, 0, sizeof(uint32_t) << 16, 0);
+    hipLaunchKernelGGL(v.k, dim3(blocks), dim3(threads), 0, 0, d, iters);
+  }
+  (void)hipMemsetAsync(tk, 0, sizeof(uint32_t) << 16, 0);
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
