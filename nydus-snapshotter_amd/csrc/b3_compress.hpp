@@ -44,10 +44,11 @@ constexpr Sched kSched = make_sched();
 #define B3_OP3(op, a, b, x) asm volatile(op " %0, %0, %1, %2" : "+v"(a) : "v"(b), "v"(x))
 #define B3_OP2(op, a, b) asm volatile(op " %0, %0, %1" : "+v"(a) : "v"(b))
 #define B3_ROT(a, n) asm volatile("v_alignbit_b32 %0, %0, %0, " #n : "+v"(a))
-// Wave priority by run (B3_PRIO 1; 0 is the stream without it, kept for the
-// A/B like B3_LOAD128): priority 1 on the runs of 4-cycle ops (a step's last
-// rotates and the next step's add3 make one run of 8), 0 on the runs of
-// 2-cycle ops.  VALU issue between a SIMD's waves goes by priority, then age:
+// Wave priority by run (B3_PRIO 1; 0 is the stream without it, the "before"
+// build of tools/valu_prio_summary.py): priority 1 on the runs of 4-cycle ops
+// (a step's last rotates and the next step's add3 make one run of 8), 0 on
+// the runs of 2-cycle ops.  VALU issue between a SIMD's waves goes by
+// priority, then age:
 // at equal priority the oldest wave issues back to back, the others sit one
 // run behind it and a 2-cycle op never meets another wave's 2-cycle op, so
 // every instruction costs ~4 cycles.  With the flips the SIMD drains every
@@ -143,22 +144,11 @@ constexpr Sched kSched = make_sched();
     B3_ROT(v4, 7); B3_ROT(v5, 7); B3_ROT(v6, 7); B3_ROT(v7, 7);                         \
   } while (0)
 
-#ifndef B3_FOLD
-#define B3_FOLD 1
-#endif
-#ifndef B3_FAST_NT
-#define B3_FAST_NT 0
-#endif
-#ifndef B3_LOAD128
-#define B3_LOAD128 1
-#endif
-
 __device__ __forceinline__ void compress(uint32_t cv[8], const uint32_t m[16],
                                          uint32_t counter, uint32_t blen, uint32_t flags) {
   uint32_t v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3];
   uint32_t v4 = cv[4], v5 = cv[5], v6 = cv[6], v7 = cv[7];
   B3_PRIO_SLOW;
-#if B3_FOLD
   uint32_t v8, v9, v10, v11, v12, v13, v14, v15;
   {
     const uint8_t *s = kSched.s[0];
@@ -168,12 +158,6 @@ __device__ __forceinline__ void compress(uint32_t cv[8], const uint32_t m[16],
   }
 #pragma unroll
   for (int r = 1; r < 7; ++r) {
-#else
-  uint32_t v8 = IV0, v9 = IV1, v10 = IV2, v11 = IV3;
-  uint32_t v12 = counter, v13 = 0, v14 = blen, v15 = flags;
-#pragma unroll
-  for (int r = 0; r < 7; ++r) {
-#endif
     const uint8_t *s = kSched.s[r];
     B3_G4(v0, v4, v8, v12, v1, v5, v9, v13, v2, v6, v10, v14, v3, v7, v11, v15,
           m[s[0]], m[s[2]], m[s[4]], m[s[6]], m[s[1]], m[s[3]], m[s[5]], m[s[7]]);

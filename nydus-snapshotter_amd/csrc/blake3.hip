@@ -359,24 +359,17 @@ __device__ __forceinline__ int group_cv(const uint8_t *__restrict__ data, uint64
       // loops, each with its compression, one after the other.)
       const u32x4 *q = reinterpret_cast<const u32x4 *>(src + off);
       const uint32_t fl_end = CHUNK_END | ((root_group && nleaves == 1) ? ROOT : 0);
-#if B3_LOAD128
       // Both 64-B blocks of a 128-B line are loaded together (8 x 16-B loads
       // per pair of compressions): a lane's line is requested from the fabric
       // once.  Loading each block just before its compression left ~one
       // compression between the two halves of the line, long enough for the
       // L2 to evict it: 14 % of the lines were fetched twice (TCC_EA0_RDREQ_128B,
-      // profiles/r1/pmc_req_c2.json).
+      // profiles/r1/pmc_req_c2.json).  Non-temporal loads of the same line
+      // pair: C2 35 % slower, the L2 re-fetched lines
+      // (profiles/r4/ab_fastnt_r4x.json).
       for (uint32_t b = 0; b < 16; b += 2, q += 8) {
-#if B3_FAST_NT  // A/B only (default 0): the same line pair with non-temporal loads
-        const uint8_t *qb = reinterpret_cast<const uint8_t *>(q);
-        const u32x4 x0 = load_nt16(qb), x1 = load_nt16(qb + 16), x2 = load_nt16(qb + 32),
-                    x3 = load_nt16(qb + 48);
-        const u32x4 x4 = load_nt16(qb + 64), x5 = load_nt16(qb + 80), x6 = load_nt16(qb + 96),
-                    x7 = load_nt16(qb + 112);
-#else
         const u32x4 x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3];
         const u32x4 x4 = q[4], x5 = q[5], x6 = q[6], x7 = q[7];
-#endif
         m[0] = x0.x; m[1] = x0.y; m[2] = x0.z; m[3] = x0.w;
         m[4] = x1.x; m[5] = x1.y; m[6] = x1.z; m[7] = x1.w;
         m[8] = x2.x; m[9] = x2.y; m[10] = x2.z; m[11] = x2.w;
@@ -388,19 +381,6 @@ __device__ __forceinline__ int group_cv(const uint8_t *__restrict__ data, uint64
         m[12] = x7.x; m[13] = x7.y; m[14] = x7.z; m[15] = x7.w;
         compress(cur, m, leaf, 64, b == 14 ? fl_end : 0u);
       }
-#else
-      // unrolled by 2: keeps this loop's compressions a separate copy (the
-      // compiler otherwise merges them with the general loop's)
-#pragma unroll 2
-      for (uint32_t b = 0; b < 16; ++b, q += 4) {
-        const u32x4 x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3];
-        m[0] = x0.x; m[1] = x0.y; m[2] = x0.z; m[3] = x0.w;
-        m[4] = x1.x; m[5] = x1.y; m[6] = x1.z; m[7] = x1.w;
-        m[8] = x2.x; m[9] = x2.y; m[10] = x2.z; m[11] = x2.w;
-        m[12] = x3.x; m[13] = x3.y; m[14] = x3.z; m[15] = x3.w;
-        compress(cur, m, leaf, 64, b == 0 ? CHUNK_START : b == 15 ? fl_end : 0u);
-      }
-#endif
       if (D > 0) finish(k);
       continue;
     }
@@ -431,10 +411,6 @@ __device__ __forceinline__ int group_cv(const uint8_t *__restrict__ data, uint64
   return root_group ? 1 : 2;
 }
 
-#ifndef B3_BALANCE
-#define B3_BALANCE 1
-#endif
-
 // Compressions of leaf group j of a chunk of len bytes (its 64-B blocks plus
 // the in-group parent merges): the lane's work.
 template <int D>
@@ -448,28 +424,14 @@ __device__ __forceinline__ uint32_t group_work(uint32_t len, uint32_t j) {
   return blocks + cnt - 1;
 }
 
-#ifndef B3_WAVES_PER_EU
-#define B3_WAVES_PER_EU 0
-#endif
-
 // In-window tree levels by lane quads (defined with compress_quad below).
-#ifndef B3_WG_QUAD
-#define B3_WG_QUAD 1
-#endif
-#if B3_WG_QUAD
 __device__ __forceinline__ void wg_tree_quad(uint32_t *b0, uint32_t *b1, uint32_t *nit, bool inwg,
                                              uint32_t k, uint32_t j, uint32_t o, uint32_t c,
                                              const uint32_t cur[8], uint32_t slot,
                                              ngpu_result *__restrict__ out);
-#endif
-#if B3_WAVES_PER_EU
-#define B3_OCC __attribute__((amdgpu_waves_per_eu(B3_WAVES_PER_EU)))
-#else
-#define B3_OCC
-#endif
 
 template <int D, int LM>
-__global__ __launch_bounds__(256) B3_OCC void b3_groups(
+__global__ __launch_bounds__(256) void b3_groups(
     const uint8_t *__restrict__ data, uint64_t data_len,
     const ngpu_chunk *__restrict__ chunks, uint64_t n,
     const uint64_t *__restrict__ gbase, const uint32_t *__restrict__ gchunk,
@@ -478,9 +440,7 @@ __global__ __launch_bounds__(256) B3_OCC void b3_groups(
     const uint32_t *__restrict__ small, const uint64_t *__restrict__ nsmall,
     uint32_t *__restrict__ tree_list) {
   __shared__ uint32_t lcv[256 * 8];
-#if B3_WG_QUAD
   __shared__ uint32_t lcv2[256 * 8];  // ping-pong partner of lcv
-#endif
   // groups [0, gm): multi-group chunks in chunk order; [gm, gm + ns): the
   // single-group chunks, largest first
   const uint64_t gm = gbase[n];
@@ -491,7 +451,6 @@ __global__ __launch_bounds__(256) B3_OCC void b3_groups(
   if (blockIdx.x == 0 && threadIdx.x == 0 && (total > gridDim.x * 256ull || total > cap_g))
     note_overlap(err, total);
   uint32_t slot = threadIdx.x;  // the group of this workgroup window this lane hashes
-#if B3_BALANCE
   // Lane balance inside the window: a wave runs as long as its longest lane,
   // and the last group of a multi-group chunk is usually partial (real layers:
   // 10 % of the lanes idle).  When the window's groups differ in work, lanes
@@ -537,7 +496,6 @@ __global__ __launch_bounds__(256) B3_OCC void b3_groups(
       slot = perm[threadIdx.x];
     }
   }
-#endif
   const uint64_t g = g0 + slot;
   uint32_t cur[8], c = 0, j = 0;
   uint64_t base = 0, ng = 0;
@@ -574,52 +532,12 @@ __global__ __launch_bounds__(256) B3_OCC void b3_groups(
     d[0] = make_uint4(cur[0], cur[1], cur[2], cur[3]);
     d[1] = make_uint4(cur[4], cur[5], cur[6], cur[7]);
   }
-#if B3_WG_QUAD
   __shared__ uint32_t nit[2];
   if (threadIdx.x == 0) nit[0] = nit[1] = 0;
-#endif
   if (!__syncthreads_or(inwg)) return;
   const uint32_t o = (uint32_t)(base - g0);  // chunk's first slot in lcv
   uint32_t k = inwg ? (uint32_t)ng : 1;
-#if B3_WG_QUAD
   wg_tree_quad(lcv, lcv2, nit, inwg, k, j, o, c, cur, slot, out);
-#else
-  if (inwg) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) lcv[8 * slot + i] = cur[i];
-  }
-  for (;;) {
-    const bool active = k > 1;
-    if (!__syncthreads_or(active)) break;
-    uint32_t r[8];
-    const uint32_t p = k >> 1;
-    const bool comp = active && j < p;
-    const bool odd = active && (k & 1) && j == p;
-    if (comp) {
-      uint32_t m[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) m[i] = lcv[8 * (o + 2 * j) + i];
-      set_iv(r);
-      compress(r, m, 0, 64, PARENT | (k == 2 ? ROOT : 0));
-    }
-    if (odd) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) r[i] = lcv[8 * (o + k - 1) + i];
-    }
-    __syncthreads();
-    if (comp || odd) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) lcv[8 * (o + j) + i] = r[i];
-    }
-    if (comp && k == 2) {
-      uint4 *d = reinterpret_cast<uint4 *>(out[c].digest);
-      d[0] = make_uint4(r[0], r[1], r[2], r[3]);
-      d[1] = make_uint4(r[4], r[5], r[6], r[7]);
-      out[c].kind = NGPU_DIGESTED;
-    }
-    k = active ? p + (k & 1) : 1;
-  }
-#endif
 }
 
 // Upper levels: one workgroup per chunk with more than one leaf group.
@@ -644,13 +562,7 @@ constexpr int kQuadThreads = 256;           // 64 quads = 64 leaves per workgrou
 // builds alternated on one box): a 32 MiB layer (32,768 leaves + its chunks)
 // missed the old 32K limit by its chunk count: 467-486 GB/s on b3_groups<0>,
 // 577 on the quad path; 48 MiB ties (0.032 ms both ways).
-#ifndef B3_QUAD_PF
-#define B3_QUAD_PF 1
-#endif
-#ifndef B3_QUAD_MAX_LEAVES
-#define B3_QUAD_MAX_LEAVES 40960
-#endif
-constexpr uint64_t kQuadMaxLeaves = B3_QUAD_MAX_LEAVES;
+constexpr uint64_t kQuadMaxLeaves = 40960;
 constexpr int kQP1 = 0x39, kQP2 = 0x4E, kQP3 = 0x93;  // quad_perm: lane i reads lane i+1/+2/+3
 
 template <int P>
@@ -712,7 +624,6 @@ constexpr QuadSched make_quad_sched() {
 }
 constexpr QuadSched kQuadSched = make_quad_sched();
 
-#if B3_WG_QUAD
 // The upper levels of the chunks whose groups all sit in one b3_groups
 // workgroup.  Each level lists its parents in LDS (source pair, destination
 // slot, ROOT, chunk) and the workgroup's 64 quads take them one per quad
@@ -785,7 +696,6 @@ __device__ __forceinline__ void wg_tree_quad(uint32_t *b0, uint32_t *b1, uint32_
     k = active ? p + (k & 1) : 1;
   }
 }
-#endif
 
 // The lane's 16 bytes of a block: valid (0..16) bytes, zero padded; byte
 // loads when partial or unaligned (never past the chunk).
@@ -821,7 +731,6 @@ __device__ __forceinline__ void quad_leaf(const uint8_t *__restrict__ data, cons
   const uint32_t ivq = q == 0 ? iv_lo[0] : q == 1 ? iv_lo[1] : q == 2 ? iv_lo[2] : iv_lo[3];
   uint32_t x = ivq, y = q == 0 ? iv_hi[0] : q == 1 ? iv_hi[1] : q == 2 ? iv_hi[2] : iv_hi[3];
   auto valid = [&](uint32_t b) { return (int)min(16u, (uint32_t)max(0, (int)llen - (int)(64 * b + 16 * q))); };
-#if B3_QUAD_PF
   // the whole leaf in flight at once (16 x 16 B per lane): one memory latency
   // per leaf instead of one per block behind a one-block prefetch
   u32x4 wb[16];
@@ -836,12 +745,6 @@ __device__ __forceinline__ void quad_leaf(const uint8_t *__restrict__ data, cons
   for (uint32_t b = 0; b < 16; ++b) {
     if (b >= nb) continue;  // (not break: keeps the loop unrolled, wb in registers)
     const u32x4 w = wb[b];
-#else
-  u32x4 w = load16(src, valid(0));
-  for (uint32_t b = 0; b < nb; ++b) {
-    u32x4 nx = w;
-    if (b + 1 < nb) nx = load16(src + 64 * (b + 1), valid(b + 1));  // next block in flight
-#endif
     *reinterpret_cast<u32x4 *>(blk + 4 * q) = w;
     // the quad's four stores are in this wave's LDS queue ahead of its loads
     asm volatile("" ::: "memory");
@@ -854,9 +757,6 @@ __device__ __forceinline__ void quad_leaf(const uint8_t *__restrict__ data, cons
                            (b + 1 == nb ? (CHUNK_END | (root_group ? ROOT : 0u)) : 0u);
     const uint32_t dq = q == 0 ? j : q == 1 ? 0u : q == 2 ? bl : flags;
     compress_quad(x, y, m, ivq, dq);
-#if !B3_QUAD_PF
-    w = nx;
-#endif
   }
   if (root_group) {
     uint32_t *d = reinterpret_cast<uint32_t *>(out[c].digest);
@@ -912,13 +812,10 @@ __global__ __launch_bounds__(kQuadThreads) void b3_quad_leaves(
   }
 }
 
-#ifndef B3_QUAD_GROUPS
-#define B3_QUAD_GROUPS 1
-#endif
-#if B3_QUAD_GROUPS
 // Small calls (<= kSmallPlanChunks chunks, quad path): the planning is done
-// by every workgroup for itself in LDS, so the call has no planning kernel,
-// and the two lowest tree levels of every multi-leaf chunk run inside the
+// by every workgroup for itself in LDS, so the call has no planning kernel
+// (one launch less: ~4 us of host enqueue and ~5 us of a small layer's GPU
+// time), and the two lowest tree levels of every multi-leaf chunk run inside the
 // wave that hashed their leaves.
 //   * Slots: the multi-leaf chunks first, in chunk order, each taking its leaf
 //     count rounded up to 4 slots (so its leaves 4i..4i+3 are 4 adjacent
@@ -1097,112 +994,6 @@ __global__ __launch_bounds__(kQuadThreads) void b3_quad_planned(
 
 // Slots b3_quad_planned may need: every multi-leaf chunk rounded up to 4.
 uint64_t quad_planned_slots(uint64_t n, uint64_t data_len) { return data_len / kLeaf + 4 * n + 1; }
-#else
-// Small calls (<= kSmallPlanChunks chunks, quad path): the planning is done
-// by every workgroup for itself in LDS, so the call has no planning kernel
-// (one launch less: ~4 us of host enqueue and ~5 us of a small layer's GPU
-// time).  Leaves are numbered in chunk order (gpre = exclusive scan of each
-// chunk's leaf count, a zero-length chunk counting one), quad g takes leaf
-// g - gpre[c] of the chunk c with gpre[c] <= g < gpre[c + 1].  Workgroup 0
-// also writes what the later kernels and the host read: groups[0..n] = gpre,
-// the multi-leaf chunks in chunk order as b3_tree's queue, and the call's
-// counters (stats[7] = bad descriptors, stats[9] = queued chunks, the rest
-// zero) -- all deterministic, no atomics.
-constexpr int kFusedItems = (int)(kSmallPlanChunks / kQuadThreads);
-static_assert(kFusedItems * kQuadThreads == (int)kSmallPlanChunks, "one item set");
-
-__global__ __launch_bounds__(kQuadThreads) void b3_quad_planned(
-    const uint8_t *__restrict__ data, uint64_t data_len, const ngpu_chunk *__restrict__ chunks,
-    uint64_t n, uint64_t cap_g, uint32_t *__restrict__ cv_out, ngpu_result *__restrict__ out,
-    uint64_t *__restrict__ groups, uint64_t *__restrict__ stats, uint32_t *__restrict__ tree_list) {
-  __shared__ __attribute__((aligned(16))) uint32_t qmsg[kQuadThreads / 4 * 16];
-  __shared__ uint32_t gpre[kSmallPlanChunks + 1];
-  __shared__ uint32_t wsum[3][kQuadThreads / 64];
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  // this thread's chunks: c0 .. c0 + kFusedItems - 1 (contiguous)
-  const uint32_t c0 = (uint32_t)t * kFusedItems;
-  uint32_t lv[kFusedItems], sum = 0, multi = 0, bad = 0, mb = 0;
-#pragma unroll
-  for (int i = 0; i < kFusedItems; ++i) {
-    const uint32_t c = c0 + i;
-    lv[i] = 0;
-    if (c < n) {
-      const ngpu_chunk ch = chunks[c];
-      const uint32_t len = ch.length;
-      const bool bd = ch.offset > data_len || len > data_len - ch.offset;
-      lv[i] = len == 0 ? 1 : (len + kLeaf - 1) / kLeaf;
-      if (bd) mb |= 1u << i;  // a bad chunk keeps its leaf numbers but is never hashed
-      multi += lv[i] > 1 && !bd;
-      bad += bd;
-    }
-    sum += lv[i];
-  }
-  // three block scans in one pass (leaves; multi-leaf chunks; bad descriptors)
-  uint32_t xs = sum, xm = multi, xb = bad;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t ys = __shfl_up(xs, o, 64), ym = __shfl_up(xm, o, 64), yb = __shfl_up(xb, o, 64);
-    if (lane >= o) xs += ys, xm += ym, xb += yb;
-  }
-  if (lane == 63) wsum[0][wid] = xs, wsum[1][wid] = xm, wsum[2][wid] = xb;
-  __syncthreads();
-  uint32_t ps = 0, pm = 0, ts = 0, tm = 0, tb = 0;
-#pragma unroll
-  for (int w = 0; w < kQuadThreads / 64; ++w) {
-    if (w < wid) ps += wsum[0][w], pm += wsum[1][w];
-    ts += wsum[0][w];
-    tm += wsum[1][w];
-    tb += wsum[2][w];
-  }
-  uint32_t run = ps + xs - sum, mrun = pm + xm - multi;
-  const bool writer = blockIdx.x == 0;
-#pragma unroll
-  for (int i = 0; i < kFusedItems; ++i) {
-    const uint32_t c = c0 + i;
-    if (c < n) {
-      gpre[c] = run;
-      if (writer) {
-        groups[c] = run;
-        if (lv[i] > 1 && !((mb >> i) & 1)) tree_list[mrun++] = c;
-      }
-    }
-    run += lv[i];
-  }
-  if (t == 0) {
-    gpre[n] = ts;
-    if (writer) groups[n] = ts;
-  }
-  // stats[8]: more leaves than the launch covers -- descriptors that overlap
-  // (a tar's file extents never do); the call then fails instead of leaving
-  // leaves unhashed
-  const uint64_t span = (uint64_t)gridDim.x * (kQuadThreads / 4);
-  const uint64_t over = ts > span || ts > cap_g ? ts : 0;
-  if (writer && t < 16)
-    stats[t] = t == kStBadDesc ? tb : t == kStTreeQueued ? tm : t == kStOverlap ? over : 0;
-  if (writer && t == 0 && tb)
-    atomicAdd((unsigned long long *)(stats + kStSticky), (unsigned long long)tb);
-  if (writer && t == 0 && over)
-    atomicMax((unsigned long long *)(stats + kStSticky + 1), (unsigned long long)over);
-  __syncthreads();
-  const uint32_t q = t & 3, quad = t >> 2;
-  const uint64_t g = blockIdx.x * (uint64_t)(kQuadThreads / 4) + quad;
-  if (g >= ts || g >= cap_g) return;  // per quad: its four lanes leave together
-  // the chunk holding leaf g: the last c with gpre[c] <= g
-  uint32_t lo = 0, hi = (uint32_t)n;  // gpre[lo] <= g < gpre[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (gpre[mid] <= g) lo = mid;
-    else hi = mid;
-  }
-  const uint32_t c = lo, j = (uint32_t)(g - gpre[c]);
-  const ngpu_chunk ch = chunks[c];
-  if (ch.offset > data_len || ch.length > data_len - ch.offset) return;  // counted above
-  quad_leaf(data, ch, c, j, gpre[c + 1] - gpre[c] == 1, g, q, qmsg + quad * 16, cv_out, out);
-}
-
-// Slots b3_quad_planned may need.
-uint64_t quad_planned_slots(uint64_t n, uint64_t data_len) { return data_len / kLeaf + 2 * n + 1; }
-#endif
 
 // 1024 threads = 256 quads: every level of a 1024-CV tile (<= 512 parents)
 // runs as compress_quad in at most two passes.  A chain of ~10 levels is the
@@ -1219,9 +1010,6 @@ uint64_t quad_planned_slots(uint64_t n, uint64_t data_len) { return data_len / k
 // us), for one more pass on the widest level of a 1 MiB chunk.
 constexpr int kTreeThreads = 1024;
 constexpr int kTile = 1024;  // CVs per LDS tile (32 KiB)
-#ifndef B3_TREE_NARROW
-#define B3_TREE_NARROW 1
-#endif
 constexpr int kTreeThreadsNarrow = 256;
 constexpr uint64_t kTreeNarrowMinChunks = 512;
 constexpr int kTileNarrow = 512;
@@ -1439,7 +1227,7 @@ bool launch_blake3(const uint8_t *data, const ngpu_chunk *chunks, uint64_t n,
   // of few chunks keeps the wide workgroup: its longest tree's widest level
   // is one pass there, two here (C1 206 -> 203, l32m 628 -> 608 narrow;
   // log-normal 30 MB layers of ~2,500 chunks 298 -> 329 GB/s)
-  if (B3_QUAD_GROUPS && B3_TREE_NARROW && n >= kTreeNarrowMinChunks &&
+  if (n >= kTreeNarrowMinChunks &&
       blake3_planned_in_leaves(n, data_len, D, ws) && chunk_size &&
       chunk_size / (4 * kLeaf) <= (uint64_t)kTileNarrow) {
     const uint64_t blocks = n < 8192 ? n : 8192;

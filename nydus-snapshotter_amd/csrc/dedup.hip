@@ -79,19 +79,6 @@ __device__ void ht_insert_min(uint64_t *table, uint64_t mask,
   }
 }
 
-// Returns the stored (smallest) id for digest d, or kNone.
-template <int STRIDE>
-__device__ uint32_t ht_lookup(const uint64_t *table, uint64_t mask,
-                              const uint8_t *keys, const uint32_t d[8]) {
-  const uint32_t tag = digest_tag(d);
-  for (uint64_t p = digest_bucket(d) & mask;; p = (p + 1) & mask) {
-    const uint64_t s = table[p];
-    if (s == kEmpty) return kNone;
-    if ((uint32_t)(s >> 32) == tag && digest_eq<STRIDE>(keys, (uint32_t)s, d))
-      return (uint32_t)s;
-  }
-}
-
 // Entries [first, m) into the table.  A build inserts [0, m) into a cleared
 // table; an in-place dict extend inserts its new ids into the live one, after
 // the launch that wrote their records (the duplicate check below reads other
@@ -104,27 +91,14 @@ __global__ void dict_insert(const DictRec *__restrict__ rec, uint64_t first, uin
     ht_insert_min<sizeof(DictRec)>(table, mask, reinterpret_cast<const uint8_t *>(rec), (uint32_t)e);
 }
 
-__device__ __forceinline__ uint32_t dict_lookup(const DictDevice &dict, const uint32_t d[8]) {
-  return ht_lookup<sizeof(DictRec)>(dict.table, dict.mask,
-                                    reinterpret_cast<const uint8_t *>(dict.rec), d);
-}
-
-// The hit record of local entry e (global id through gid for node shards).
-__device__ __forceinline__ ngpu_dict_hit dict_hit_of(const DictDevice &dict, uint32_t e) {
-  if (e == kNone) return ngpu_dict_hit{kNone, 0, 0, 0, 0};
-  // the record's second half: the line the digest compare just brought in
-  const uint4 f = reinterpret_cast<const uint4 *>(dict.rec + e)[2];  // usize, blob, index, gid
-  const uint64_t uo = dict.rec[e].uoff;
-  return ngpu_dict_hit{f.w, f.z, f.y, f.x, uo};
-}
-
 // Lookup + hit in one pass: at a tag match the whole 64-B record is read (its
 // four loads issued together), compared, and the hit built from registers.
-// dict_hit_of(dict_lookup()) re-read the record's second half after the
+// Looking the entry up first and building the hit from it afterwards (the
+// earlier form, removed) re-read the record's second half after the
 // probe loop, i.e. after the wave's LONGEST chain had finished; by then the
 // line had often left the L2 (random lines turn the L2 over in a few us) and
 // the re-read went to HBM: +0.35 line per probe at 30 % hits (1.94 -> 1.60;
-// dict_probe_variant RV 2..4 took the probe apart, tools/probe_sweep.py).
+// probe variants that took the probe apart showed it, tools/probe_sweep.py).
 // Slots whose id is >= dict.m are skipped unread: that is what keeps a handle
 // blind to in-place appends behind it (dict.hip "dict extend"; for a node shard
 // dict.m is the part's local count, as table ids are local).
@@ -154,6 +128,10 @@ __device__ __forceinline__ ngpu_dict_hit dict_find(const DictDevice &dict, const
 // write covers no line in one instruction, and the L2 then read every hit
 // line from HBM before merging (~0.19 of the probe's ~1.96 line requests;
 // tools/probe_sweep.py).  256 threads per workgroup (launch_dict_probe).
+// Two to four chains per lane, the queries held in LDS, and 16 lanes per
+// query reading a whole bucket line were each measured against it and lost
+// (DESIGN.md §3 "dict probe"; profiles/r4/probe_multi/,
+// profiles/r2/probe_coop_ab.txt).
 __global__ __launch_bounds__(256) void dict_probe_records(const uint8_t *__restrict__ digests,
                                                           uint64_t stride, uint64_t n,
                                                           DictDevice dict,
@@ -186,310 +164,6 @@ __global__ __launch_bounds__(256) void dict_probe_records(const uint8_t *__restr
       reinterpret_cast<uint2 *>(dst)[i] = reinterpret_cast<const uint2 *>(stage)[i];
   }
 }
-
-// Measured-losing A/B probes (dict_probe_multi, dict_probe_multi_lds,
-// dict_probe_variant, dict_probe_coop; DESIGN.md §3 "dict probe") are built
-// only with -DNGPU_PROBE_AB=1 (scripts/build_ab.sh), never into the product
-// library; their launch knobs (NGPU_PROBE_VARIANT / NGPU_PROBE_COOP) exist
-// only in such a build.  They do not carry dict_find's `id >= dict.m` skip, so
-// an A/B build must not probe a handle that an in-place dict extend has grown
-// past (ngpu_dict_extend); the tools that use them build their dicts in one go.
-#ifndef NGPU_PROBE_AB
-#define NGPU_PROBE_AB 0
-#endif
-#if NGPU_PROBE_AB
-// K queries per thread, their probe chains stepped in lockstep: each step
-// issues the K slot loads (and the K record loads of tag matches) together,
-// so a wave has K independent random requests in flight where
-// dict_probe_records has one.  Same decisions as dict_find (slots in chain
-// order, first equal record, stop at an empty slot).  Hits staged as there.
-template <int K>
-__global__ __launch_bounds__(256) void dict_probe_multi(const uint8_t *__restrict__ digests,
-                                                        uint64_t stride, uint64_t n,
-                                                        DictDevice dict,
-                                                        ngpu_dict_hit *__restrict__ hits) {
-  __shared__ uint4 stage[K * 256 * sizeof(ngpu_dict_hit) / 16];
-  const uint64_t q0 = blockIdx.x * (256ull * K);
-  uint32_t d[K][8], tag[K];
-  uint64_t pos[K];
-  bool live[K];
-  ngpu_dict_hit h[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const uint64_t q = q0 + threadIdx.x + 256u * j;
-    live[j] = q < n && dict.m;
-    h[j] = ngpu_dict_hit{kNone, 0, 0, 0, 0};
-    uint4 a = make_uint4(0, 0, 0, 0), b = a;
-    if (live[j]) {
-      const uint4 *p = reinterpret_cast<const uint4 *>(digests + q * stride);
-      a = p[0];
-      b = p[1];
-    }
-    d[j][0] = a.x; d[j][1] = a.y; d[j][2] = a.z; d[j][3] = a.w;
-    d[j][4] = b.x; d[j][5] = b.y; d[j][6] = b.z; d[j][7] = b.w;
-    tag[j] = digest_tag(d[j]);
-    pos[j] = digest_bucket(d[j]) & dict.mask;
-  }
-  for (;;) {
-    uint64_t sv[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) sv[j] = live[j] ? dict.table[pos[j]] : kEmpty;
-    bool cand[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      if (sv[j] == kEmpty) live[j] = false;
-      cand[j] = live[j] && (uint32_t)(sv[j] >> 32) == tag[j];
-    }
-    uint4 ra[K], rb[K], rf[K];
-    uint64_t ru[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      if (cand[j]) {
-        const uint4 *r = reinterpret_cast<const uint4 *>(dict.rec + (uint32_t)sv[j]);
-        ra[j] = r[0];
-        rb[j] = r[1];
-        rf[j] = r[2];
-        ru[j] = dict.rec[(uint32_t)sv[j]].uoff;
-      }
-    }
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      if (cand[j] && ((ra[j].x ^ d[j][0]) | (ra[j].y ^ d[j][1]) | (ra[j].z ^ d[j][2]) |
-                      (ra[j].w ^ d[j][3]) | (rb[j].x ^ d[j][4]) | (rb[j].y ^ d[j][5]) |
-                      (rb[j].z ^ d[j][6]) | (rb[j].w ^ d[j][7])) == 0) {
-        h[j] = ngpu_dict_hit{rf[j].w, rf[j].z, rf[j].y, rf[j].x, ru[j]};
-        live[j] = false;
-      }
-      if (live[j]) pos[j] = (pos[j] + 1) & dict.mask;
-      any |= live[j];
-    }
-    if (!any) break;
-  }
-#pragma unroll
-  for (int j = 0; j < K; ++j)
-    if (q0 + threadIdx.x + 256u * j < n)
-      reinterpret_cast<ngpu_dict_hit *>(stage)[threadIdx.x + 256u * j] = h[j];
-  __syncthreads();
-  const uint64_t m = n - q0 < 256ull * K ? n - q0 : 256ull * K;
-  const uint32_t bytes = (uint32_t)m * (uint32_t)sizeof(ngpu_dict_hit);
-  uint8_t *dst = reinterpret_cast<uint8_t *>(hits + q0);
-  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-    for (uint32_t i = threadIdx.x; i < bytes / 16; i += 256)
-      reinterpret_cast<uint4 *>(dst)[i] = stage[i];
-    if ((bytes & 15) && threadIdx.x == 0)
-      reinterpret_cast<uint2 *>(dst + (bytes & ~15u))[0] =
-          reinterpret_cast<const uint2 *>(stage)[(bytes & ~15u) / 8];
-  } else {
-    for (uint32_t i = threadIdx.x; i < bytes / 8; i += 256)
-      reinterpret_cast<uint2 *>(dst)[i] = reinterpret_cast<const uint2 *>(stage)[i];
-  }
-}
-
-// dict_probe_multi with the queries kept in LDS instead of registers (the
-// compare reads them back), so K = 2 fits 8 waves per SIMD without spills.
-template <int K>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void
-dict_probe_multi_lds(const uint8_t *__restrict__ digests, uint64_t stride, uint64_t n,
-                     DictDevice dict, ngpu_dict_hit *__restrict__ hits) {
-  __shared__ uint4 qs[K * 256 * 2];  // the queries, then (after a barrier) the staged hits
-  uint4 *stage = qs;
-  const uint64_t q0 = blockIdx.x * (256ull * K);
-  uint32_t tag[K];
-  uint64_t pos[K];
-  bool live[K];
-  ngpu_dict_hit h[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const uint32_t t = threadIdx.x + 256u * j;
-    const uint64_t q = q0 + t;
-    live[j] = q < n && dict.m;
-    h[j] = ngpu_dict_hit{kNone, 0, 0, 0, 0};
-    uint4 a = make_uint4(0, 0, 0, 0), b = a;
-    if (live[j]) {
-      const uint4 *p = reinterpret_cast<const uint4 *>(digests + q * stride);
-      a = p[0];
-      b = p[1];
-    }
-    qs[2 * t] = a;
-    qs[2 * t + 1] = b;
-    const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    tag[j] = digest_tag(d);
-    pos[j] = digest_bucket(d) & dict.mask;
-  }
-  for (;;) {
-    uint64_t sv[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) sv[j] = live[j] ? dict.table[pos[j]] : kEmpty;
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      if (sv[j] == kEmpty) live[j] = false;
-      if (live[j] && (uint32_t)(sv[j] >> 32) == tag[j]) {
-        const uint32_t e = (uint32_t)sv[j];
-        const uint4 *r = reinterpret_cast<const uint4 *>(dict.rec + e);
-        const uint4 ra = r[0], rb = r[1], rf = r[2];
-        const uint64_t ru = dict.rec[e].uoff;
-        const uint32_t t = threadIdx.x + 256u * j;
-        const uint4 a = qs[2 * t], b = qs[2 * t + 1];
-        if (((ra.x ^ a.x) | (ra.y ^ a.y) | (ra.z ^ a.z) | (ra.w ^ a.w) | (rb.x ^ b.x) |
-             (rb.y ^ b.y) | (rb.z ^ b.z) | (rb.w ^ b.w)) == 0) {
-          h[j] = ngpu_dict_hit{rf.w, rf.z, rf.y, rf.x, ru};
-          live[j] = false;
-        }
-      }
-      if (live[j]) pos[j] = (pos[j] + 1) & dict.mask;
-      any |= live[j];
-    }
-    if (!any) break;
-  }
-  __syncthreads();  // every query compare of the workgroup is done with qs
-#pragma unroll
-  for (int j = 0; j < K; ++j)
-    if (q0 + threadIdx.x + 256u * j < n)
-      reinterpret_cast<ngpu_dict_hit *>(stage)[threadIdx.x + 256u * j] = h[j];
-  __syncthreads();
-  const uint64_t m = n - q0 < 256ull * K ? n - q0 : 256ull * K;
-  const uint32_t bytes = (uint32_t)m * (uint32_t)sizeof(ngpu_dict_hit);
-  uint8_t *dst = reinterpret_cast<uint8_t *>(hits + q0);
-  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-    for (uint32_t i = threadIdx.x; i < bytes / 16; i += 256)
-      reinterpret_cast<uint4 *>(dst)[i] = stage[i];
-    if ((bytes & 15) && threadIdx.x == 0)
-      reinterpret_cast<uint2 *>(dst + (bytes & ~15u))[0] =
-          reinterpret_cast<const uint2 *>(stage)[(bytes & ~15u) / 8];
-  } else {
-    for (uint32_t i = threadIdx.x; i < bytes / 8; i += 256)
-      reinterpret_cast<uint2 *>(dst)[i] = reinterpret_cast<const uint2 *>(stage)[i];
-  }
-}
-
-// A/B variants of the same probe (NGPU_PROBE_VARIANT, read per call; bench /
-// tools/probe_sweep.py): where do the line requests beyond query + slot +
-// record come from?  QV: the workgroup's queries (stride 32) are read into
-// LDS with lane-contiguous 16-B loads -- one instruction per line -- instead
-// of two 16-B loads per lane, each touching every query line of the wave.
-// RV: a tag-matched record is read and compared 16 B at a time (the second
-// half only if the first matched) instead of two loads issued together.
-// RV 2..4 take the probe apart (their decisions are NOT the dict's: request
-// counting only, never parity): 2 trusts the tag (no compare, the hit record
-// still read), 3 trusts the tag and reads no record, 4 reads only the home
-// slot (no chain, no record).
-template <int QV, int RV>
-__global__ __launch_bounds__(256) void dict_probe_variant(const uint8_t *__restrict__ digests,
-                                                          uint64_t stride, uint64_t n,
-                                                          DictDevice dict,
-                                                          ngpu_dict_hit *__restrict__ hits) {
-  __shared__ uint4 qs[QV ? 512 : 1];
-  const uint64_t q0 = blockIdx.x * 256ull;
-  const uint64_t q = q0 + threadIdx.x;
-  uint32_t d[8] = {};
-  if (QV && stride == 32) {
-    const uint64_t m = n - q0 < 256 ? n - q0 : 256;
-    const uint4 *src = reinterpret_cast<const uint4 *>(digests + q0 * 32);
-    for (uint32_t i = threadIdx.x; i < 2 * m; i += 256) qs[i] = src[i];
-    __syncthreads();
-    if (q < n) {
-      const uint4 a = qs[2 * threadIdx.x], b = qs[2 * threadIdx.x + 1];
-      d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
-    }
-  } else if (q < n) {
-    const uint4 *p = reinterpret_cast<const uint4 *>(digests + q * stride);
-    const uint4 a = p[0], b = p[1];
-    d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
-  }
-  if (q >= n) return;
-  uint32_t e = kNone;
-  if (dict.m) {
-    const uint32_t tag = digest_tag(d);
-    for (uint64_t pos = digest_bucket(d) & dict.mask;; pos = (pos + 1) & dict.mask) {
-      const uint64_t sv = dict.table[pos];
-      if (RV == 4) {
-        if (sv != kEmpty && (uint32_t)(sv >> 32) == tag) e = (uint32_t)sv;
-        break;
-      }
-      if (sv == kEmpty) break;
-      if ((uint32_t)(sv >> 32) != tag) continue;
-      if (RV == 2 || RV == 3) {
-        e = (uint32_t)sv;
-        break;
-      }
-      const uint4 *r = reinterpret_cast<const uint4 *>(dict.rec + (uint32_t)sv);
-      bool eq;
-      if (RV == 1) {
-        const uint4 a = r[0];
-        eq = ((a.x ^ d[0]) | (a.y ^ d[1]) | (a.z ^ d[2]) | (a.w ^ d[3])) == 0;
-        if (eq) {
-          const uint4 b = r[1];
-          eq = ((b.x ^ d[4]) | (b.y ^ d[5]) | (b.z ^ d[6]) | (b.w ^ d[7])) == 0;
-        }
-      } else {
-        const uint4 a = r[0], b = r[1];
-        eq = ((a.x ^ d[0]) | (a.y ^ d[1]) | (a.z ^ d[2]) | (a.w ^ d[3]) | (b.x ^ d[4]) |
-              (b.y ^ d[5]) | (b.z ^ d[6]) | (b.w ^ d[7])) == 0;
-      }
-      if (eq) {
-        e = (uint32_t)sv;
-        break;
-      }
-    }
-  }
-  if (RV >= 3)
-    hits[q] = ngpu_dict_hit{e, 0, 0, 0, 0};
-  else
-    hits[q] = dict_hit_of(dict, e);
-}
-
-// The wavefront-cooperative form of the same lookup (the north star's
-// "chunk-dict hash table ... probed with wavefront-cooperative open
-// addressing"; A/B against dict_probe_records, NGPU_PROBE_COOP=1): 16 lanes
-// per query read 16 consecutive slots from the query's bucket in one
-// coalesced access, ballot for the first empty slot and the tag matches
-// before it, and verify those in probe order -- the decisions of sequential
-// linear probing, with the slot reads of a probe run side by side instead of
-// one dependent load per slot.
-__global__ __launch_bounds__(256) void dict_probe_coop(const uint8_t *__restrict__ digests,
-                                                       uint64_t stride, uint64_t n,
-                                                       DictDevice dict,
-                                                       ngpu_dict_hit *__restrict__ hits) {
-  const uint64_t q = (blockIdx.x * 256ull + threadIdx.x) >> 4;
-  const uint32_t sub = threadIdx.x & 15, grp = (threadIdx.x & 63) >> 4;
-  const bool live = q < n;
-  uint32_t e = kNone;
-  if (live && dict.m) {
-    const uint4 *p = reinterpret_cast<const uint4 *>(digests + q * stride);
-    const uint4 a = p[0], b = p[1];
-    const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const uint32_t tag = digest_tag(d);
-    uint64_t pos = digest_bucket(d) & dict.mask;
-    for (;;) {
-      const uint64_t sv = dict.table[(pos + sub) & dict.mask];
-      const bool empty = sv == kEmpty, match = !empty && (uint32_t)(sv >> 32) == tag;
-      // this group's 16 bits of the wave's ballots (a wave holds 4 groups;
-      // groups of one wave may run different numbers of rounds)
-      const uint32_t me = (uint32_t)(__ballot(empty) >> (16 * grp)) & 0xFFFFu;
-      uint32_t mm = (uint32_t)(__ballot(match) >> (16 * grp)) & 0xFFFFu;
-      const uint32_t fe = me ? (uint32_t)__builtin_ctz(me) : 16u;
-      mm &= (1u << fe) - 1u;
-      bool found = false;
-      while (mm) {
-        const uint32_t i = (uint32_t)__builtin_ctz(mm);
-        const uint32_t id = (uint32_t)__shfl(sv, (int)(16 * grp + i), 64);
-        if (digest_eq<sizeof(DictRec)>(reinterpret_cast<const uint8_t *>(dict.rec), id, d)) {
-          e = id;
-          found = true;
-          break;
-        }
-        mm &= mm - 1;
-      }
-      if (found || fe < 16) break;
-      pos += 16;
-    }
-  }
-  if (live && sub == 0) hits[q] = dict_hit_of(dict, e);
-}
-
-#endif  // NGPU_PROBE_AB
 
 // RAFS v6 chunk-info records (80 B: block_id[32], blob_index, flags,
 // compressed_size, uncompressed_size, compressed_offset, uncompressed_offset,
@@ -1376,31 +1050,6 @@ void launch_dict_probe(const uint8_t *digests, uint64_t stride, uint64_t n,
                        const DictDevice &dict, ngpu_dict_hit *hits, hipStream_t s) {
   if (n == 0) return;
   const dim3 g((unsigned)((n + 255) / 256));
-#if NGPU_PROBE_AB
-  // A/B knob, read per call (bench.py probe_roofline; 2.6x slower)
-  const char *coop = getenv("NGPU_PROBE_COOP");
-  if (coop && coop[0] == '1') {
-    hipLaunchKernelGGL(dict_probe_coop, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, s,
-                       digests, stride, n, dict, hits);
-    return;
-  }
-  const char *var = getenv("NGPU_PROBE_VARIANT");
-  const int v = var ? atoi(var) : 0;
-  switch (v) {
-    case 1: hipLaunchKernelGGL((dict_probe_variant<1, 0>), g, dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 2: hipLaunchKernelGGL((dict_probe_variant<0, 1>), g, dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 3: hipLaunchKernelGGL((dict_probe_variant<1, 1>), g, dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 4: hipLaunchKernelGGL((dict_probe_variant<0, 0>), g, dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 5: hipLaunchKernelGGL((dict_probe_variant<0, 2>), g, dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 6: hipLaunchKernelGGL((dict_probe_variant<0, 3>), g, dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 7: hipLaunchKernelGGL((dict_probe_variant<0, 4>), g, dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 8: hipLaunchKernelGGL((dict_probe_multi<2>), dim3((unsigned)((n + 511) / 512)), dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 9: hipLaunchKernelGGL((dict_probe_multi<4>), dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 10: hipLaunchKernelGGL((dict_probe_multi_lds<2>), dim3((unsigned)((n + 511) / 512)), dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    case 11: hipLaunchKernelGGL((dict_probe_multi_lds<3>), dim3((unsigned)((n + 767) / 768)), dim3(256), 0, s, digests, stride, n, dict, hits); return;
-    default: break;
-  }
-#endif
   hipLaunchKernelGGL(dict_probe_records, g, dim3(256), 0, s, digests, stride, n, dict, hits);
 }
 
@@ -1685,16 +1334,7 @@ void launch_dedup(const ngpu_chunk *chunks, uint64_t n, const DictDevice &dict,
                     reinterpret_cast<uint64_t *>(st), nst, ws.intra, icap, ts, ntw,
                     ws.newflag, ws.uoff, ws.nbytes, ws.ndict, total, ws.stats};
   if (small && single && nbo <= kLdsBlobs) {  // one layer: the whole stage in LDS
-#if NGPU_PROBE_AB
-    // NGPU_DEDUP_LDS_THREADS=1024: the wide workgroup for every size (A/B knob)
-    static const bool wide = [] {
-      const char *v = getenv("NGPU_DEDUP_LDS_THREADS");
-      return v && atoi(v) == 1024;
-    }();
-#else
-    constexpr bool wide = false;
-#endif
-    if (n <= 256 && !wide)
+    if (n <= 256)
       hipExtLaunchKernelGGL(dedup_small_lds<256>, dim3(1), dim3(256), 0, s, nullptr, ev_end, 0,
                             chunks, n, dict, hits, n_blobs, align, st, out, ws.stats);
     else

@@ -1,9 +1,10 @@
 #!/bin/bash
 # Build A/B variants of libnydusgpu.so that differ only in one source's
-# compile flags (AB_SRC, default blake3; AB_SRC=dedup with -DNGPU_PROBE_AB=1
-# for the dict-probe variants), into nydus-snapshotter_amd/build/ab/NAME.so
-# (run here, on the CPU).
-# usage: [AB_SRC=dedup] scripts/build_ab.sh NAME "-DFLAG=V ..." [NAME "-D..."] ...
+# compile flags (AB_SRC, default blake3), into
+# nydus-snapshotter_amd/build/ab/NAME.so (run here, on the CPU).  The
+# switches a build can flip: tools/README.md "Build switches" (-DB3_PRIO=0,
+# -DNGPU_DIAG_NOLOAD=1).
+# usage: [AB_SRC=blake3] scripts/build_ab.sh NAME "-DFLAG=V ..." [NAME "-D..."] ...
 set -eu
 cd "$(dirname "$0")/../nydus-snapshotter_amd"
 make -s libnydusgpu.so

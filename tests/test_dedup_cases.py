@@ -278,7 +278,7 @@ def select_path(n, layers, grid_flag, dict_blobs):
         dedup = f.read()
     small_chunks, small_layers = _const(common, "kSmallDedupChunks"), _const(common, "kSmallDedupLayers")
     lds_blobs = _const(dedup, "kLdsBlobs")
-    m = re.search(r"if \(n <= (\d+) && !wide\)\s*hipExtLaunchKernelGGL\(dedup_small_lds<(\d+)>", dedup)
+    m = re.search(r"if \(n <= (\d+)\)\s*hipExtLaunchKernelGGL\(dedup_small_lds<(\d+)>", dedup)
     assert m and m.group(1) == m.group(2)
     narrow = int(m.group(1))
     assert (small_chunks, small_layers, lds_blobs, narrow) == (4096, 64, 1024, 256)
