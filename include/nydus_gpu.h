@@ -919,6 +919,66 @@ int ngpu_node_dict_export(ngpu_node *node, const ngpu_dict *d, void *records, ui
 int ngpu_node_dict_create(ngpu_node *node, const void *records, uint64_t n,
                           const void *blob_table, uint32_t n_blobs, uint32_t mode,
                           ngpu_dict **out);
+/* ---- node dict remode: switch replicated and partitioned on the GPUs (additive in ABI 7) ----
+ * out behaves exactly as ngpu_node_dict_create(node, R, B, mode) does, where R and
+ * B are what ngpu_node_dict_export(base) returns: for every probe, Pack,
+ * ngpu_node_process_device / _step, Check, export and save, and for every later
+ * extend, fold, retire and distill.  Rows, global entry ids, blob indices, the blob
+ * table (iff base has one) and the node handle's placement rows (iff base keeps
+ * them) are unchanged; only where the rows live differs.  The rows never pass
+ * through the host.  `mode` takes the values ngpu_node_dict_create takes, with its
+ * rules: both exchange bits together is NGPU_EINVAL, ROUTED without peer access
+ * falls back to the copy exchange, exchange bits on REPLICATE are ignored.
+ *
+ * Replicated -> partitioned (split): every part works from the replica on its own
+ * device -- no peer traffic -- and keeps the rows whose digest it owns, in table
+ * order, with their entry ids in base.  Partitioned -> replicated (join): every
+ * replica gets all entries(base) rows, row g at position g.  The global ids are
+ * walked in windows of opt->window_records ids (0: the library's default, 2^20);
+ * a window is one slice per part, the other parts' slices reach the replica by
+ * hipMemcpyPeerAsync into one of two staging windows (2 x window_records x 64 B per
+ * replica, whatever the dict holds; (W - 1) / W x entries x 64 B cross the links per
+ * replica), its own slice is read where it lies, and the first entry of a digest
+ * still wins.  The same mode as base's is the compacting copy
+ * ngpu_node_dict_retire_parts gives for n == 0, with the exchange `mode` asks for.
+ *
+ * Only the handle's own entries(base) rows count: rows a later in-place extend or
+ * fold appended to the same storages are not seen.  base is only read and not
+ * released: probes, Packs and in-place extends of it may run meanwhile.  Every part
+ * of out sits on a storage of its own with ngpu_dict_retire's room (s + s / 2
+ * record slots for its s rows), the node handle on placement rows with the same
+ * room, so later extends and folds append in place.  The device work runs on
+ * streams of the library's own, one per part (the join: two), outside the engine
+ * locks; all of them are synchronised when the call returns, on every path.
+ *
+ * Rejected before any GPU work, with *out = NULL: a NULL node, base or out,
+ * opt->flags or opt->reserved non-zero, a bad mode, a plain dict, a dict of another
+ * node (NGPU_EINVAL).  Refused after device work, with everything freed and base as
+ * it was: parts whose global ids do not tile [0, entries(base)) -- an id past the
+ * end, an id held twice, a position never written (NGPU_EINVAL); an allocation
+ * that fails (NGPU_ENOMEM: a join needs entries x 64 B plus the table on every GPU,
+ * and the caller decides whether that fits).  Nothing a live handle can see is ever
+ * written.
+ * UNVERIFIED ON DISTINCT GPUs, as the node exchange above: every test so far lists
+ * one GPU several times, so the join's peer copies stay inside one HBM. */
+typedef struct {
+  uint32_t flags;          /* reserved, 0 */
+  uint32_t reserved;       /* 0 */
+  uint64_t window_records; /* join: global ids per window; 0 -> the library's default */
+} ngpu_node_dict_remode_options;   /* 16 bytes */
+int ngpu_node_dict_remode(ngpu_node *node, ngpu_dict *base, uint32_t mode,
+                          const ngpu_node_dict_remode_options *opt /* NULL: zeros */,
+                          ngpu_dict **out);
+/* What a node dict handle is (additive in ABI 7); touches no GPU.  A NULL argument,
+ * a plain dict or a dict of another node is NGPU_EINVAL, with *out zeroed. */
+typedef struct {
+  uint32_t mode;              /* NGPU_NODE_DICT_PARTITION | _REPLICATE, | the exchange in use
+                                 (NGPU_NODE_EXCHANGE_COPY or _ROUTED; replicated: neither) */
+  uint32_t parts;             /* W */
+  uint64_t entries;           /* entries(d) */
+  uint64_t part_entries[64];  /* rows the handle sees on part i (replicated: entries); 0 past W */
+} ngpu_node_dict_info;        /* 528 bytes */
+int ngpu_node_dict_info_get(const ngpu_node *node, const ngpu_dict *d, ngpu_node_dict_info *out);
 /* Device index of the node device that owns digests[32] (partitioned dicts). */
 uint32_t ngpu_node_owner(const ngpu_node *node, const uint8_t *digest);
 /* A Pack on the node's least-loaded engine (fewest open packs, ties round

@@ -392,6 +392,27 @@ void launch_node_dict_compact(const DictRec *rec, uint64_t m_o, const uint64_t *
                               uint64_t m, const uint32_t *remap, uint32_t n_blobs, DictRec *out,
                               uint64_t s_o, hipStream_t s);
 
+// dict_save.hip: off[t] for the cuts t in [0, nw] = the first row of rec[0, m_o)
+// whose global id is >= first + t x window_records (the last cut is m); the rows
+// ascend by id (a part of a partitioned node dict).
+void launch_node_save_bounds(const DictRec *rec, uint64_t m_o, uint64_t first, uint64_t m,
+                             uint64_t window_records, uint64_t nw, uint64_t *off, hipStream_t s);
+
+// node_remode.hip (ngpu_node_dict_remode, node.hip; node_remode_plan.hpp lays the
+// scratch out).  Split: keep word and count per 64 rows of a replica's rec[0, m) (a
+// row stays when part o of W owns its digest), then the scan as launch_dict_keep_scan;
+// the survivors to out[0, s_o) in order, gid = the row's position in rec.
+void launch_remode_split_keep_scan(const DictRec *rec, uint64_t m, uint32_t W, uint32_t o, uint64_t *words,
+                                   uint32_t *cnt, uint64_t *sums, hipStream_t s);
+void launch_remode_split_compact(const DictRec *rec, uint64_t m, const uint64_t *words,
+                                 const uint32_t *prefix, DictRec *out, uint64_t s_o, hipStream_t s);
+// Join: rows[0, n) of the window of ids [a, a + c) -> out[gid] (out: m rows) and bit
+// gid of bits ((m + 63) / 64 words); ctr: kRemodeCtrWords u64, both zeroed on s by
+// the caller.  Then the bitmap's set bits into ctr[kRemodeSet].
+void launch_remode_join_scatter(const DictRec *rows, uint64_t n, uint64_t a, uint64_t c, uint64_t m,
+                                DictRec *out, uint64_t *bits, uint64_t *ctr, hipStream_t s);
+void launch_remode_bitmap_count(const uint64_t *bits, uint64_t m, uint64_t *ctr, hipStream_t s);
+
 // Device workspace, grown on demand and owned by the engine.
 struct Workspace {
   uint64_t *groups = nullptr;     // n+1: leaf groups per chunk -> exclusive scan

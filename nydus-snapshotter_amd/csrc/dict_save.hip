@@ -180,8 +180,7 @@ int part_bounds(ngpu_engine *e, const ngpu_dict *p, uint64_t first, uint64_t m, 
     (void)hipGetLastError();
     return fail(e, NGPU_ENOMEM, "dict save: %llu window cuts", (unsigned long long)(nw + 1));
   }
-  hipLaunchKernelGGL(node_save_bounds, dim3(blocks_of(nw + 1)), dim3(256), 0, bs.s, p->st->rec, m_o, first, m,
-                     wr, nw, d_off);
+  launch_node_save_bounds(p->st->rec, m_o, first, m, wr, nw, d_off, bs.s);
   // (off's pageable memory: the stream is synchronised before it goes out of scope)
   const bool ok = hipGetLastError() == hipSuccess &&
                   hipMemcpyAsync(off->data(), d_off, 8 * (nw + 1), hipMemcpyDeviceToHost, bs.s) == hipSuccess;
@@ -204,6 +203,12 @@ bool trace_on() {
 }
 
 }  // namespace
+
+void launch_node_save_bounds(const DictRec *rec, uint64_t m_o, uint64_t first, uint64_t m,
+                             uint64_t window_records, uint64_t nw, uint64_t *off, hipStream_t s) {
+  hipLaunchKernelGGL(node_save_bounds, dim3(blocks_of(nw + 1)), dim3(256), 0, s, rec, m_o, first, m,
+                     window_records, nw, off);
+}
 
 // The body of both entry points.  d: a plain dict or a node dict of e's node;
 // partitioned node dicts only when node_call.

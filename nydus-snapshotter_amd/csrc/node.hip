@@ -43,6 +43,7 @@
 #include "engine_internal.hpp"
 #include "node_distill_plan.hpp"
 #include "node_fold_plan.hpp"
+#include "node_remode_plan.hpp"
 #include "node_retire_plan.hpp"
 
 using namespace ngpu;
@@ -283,27 +284,38 @@ void node_partition_records(const uint8_t *recs, uint64_t k, uint32_t W, uint64_
   }
 }
 
+// The `mode` of ngpu_node_dict_create and ngpu_node_dict_remode: replicated or
+// partitioned, and the exchange a partitioned dict runs.
+int node_dict_mode(ngpu_node *node, uint32_t mode, bool *replicated, bool *routed) {
+  ngpu_engine *e0 = node->eng[0];
+  const bool want_routed = (mode & NGPU_NODE_EXCHANGE_ROUTED) != 0;
+  if ((mode & NGPU_NODE_EXCHANGE_COPY) && want_routed)
+    return fail(e0, NGPU_EINVAL, "node dict: copy and routed exchange both asked for");
+  mode &= ~(NGPU_NODE_EXCHANGE_COPY | NGPU_NODE_EXCHANGE_ROUTED);
+  if (mode != NGPU_NODE_DICT_PARTITION && mode != NGPU_NODE_DICT_REPLICATE)
+    return fail(e0, NGPU_EINVAL, "bad node dict mode %u", mode);
+  *replicated = mode == NGPU_NODE_DICT_REPLICATE;
+  // the copy exchange (DMA peer copies) unless the routed one was asked for
+  // and every pair of devices has peer access (its kernels reach the
+  // requester's HBM): the routed exchange's peer stores have not met two
+  // distinct GPUs yet (VERDICT r5 item 6)
+  *routed = !*replicated && want_routed && node->peer_ok;
+  return 0;
+}
+
 // A node dict over records in host memory (each part built on its device's
 // own build stream, no engine lock held).
 int node_dict_build(ngpu_node *node, const uint8_t *recs, uint64_t m, const uint8_t *blobs,
                     uint32_t n_blobs, uint32_t mode, ngpu_dict **out) {
   ngpu_engine *e0 = node->eng[0];
-  const bool routed = (mode & NGPU_NODE_EXCHANGE_ROUTED) != 0;
-  if ((mode & NGPU_NODE_EXCHANGE_COPY) && routed)
-    return fail(e0, NGPU_EINVAL, "node dict: copy and routed exchange both asked for");
-  mode &= ~(NGPU_NODE_EXCHANGE_COPY | NGPU_NODE_EXCHANGE_ROUTED);
-  if (mode != NGPU_NODE_DICT_PARTITION && mode != NGPU_NODE_DICT_REPLICATE)
-    return fail(e0, NGPU_EINVAL, "bad node dict mode %u", mode);
+  bool replicated = false, routed = false;
+  if (int rc = node_dict_mode(node, mode, &replicated, &routed)) return rc;
   if (m >= 0xFFFFFFFFull) return fail(e0, NGPU_EINVAL, "chunk dict too large");
   uint32_t nb = 0;
   if (int rc = records_blob_count(e0, recs, m, n_blobs, &nb)) return rc;
   ngpu_dict *d = dict_new(e0);
-  d->replicated = mode == NGPU_NODE_DICT_REPLICATE;
-  // the copy exchange (DMA peer copies) unless the routed one was asked for
-  // and every pair of devices has peer access (its kernels reach the
-  // requester's HBM): the routed exchange's peer stores have not met two
-  // distinct GPUs yet (VERDICT r5 item 6)
-  d->routed = !d->replicated && routed && node->peer_ok;
+  d->replicated = replicated;
+  d->routed = routed;
   d->dev.m = m;
   d->dev.n_blobs = nb;
   // the global handle sits on a storage of placement rows only
@@ -996,6 +1008,370 @@ int node_dict_distill_parts(ngpu_node *node, ngpu_dict *base, uint32_t min_refs,
                               a + b + g + k, a, b, g, k);
                   },
                   out);
+}
+
+// ---- node dict remode ----------------------------------------------------------
+// ngpu_node_dict_remode: base's rows in the other mode, moved on the GPUs.  The
+// rows, their global ids and blobs, the blob table and the node handle's placement
+// rows are base's; only where the rows live differs.  The parts' streams, events,
+// scratch, waits and releases are PartsCall's, the host plan node_remode_plan.hpp,
+// the kernels node_remode.hip.
+//   split (replicated -> partitioned), part o on the replica of its own device:
+//     1. launch_remode_split_keep_scan: keep = the part owns the row's digest, the
+//        scan; s_o comes back in one 8-B copy.  All W parts are enqueued before the
+//        call's one mid-way wait.
+//     2. the verdict: sum s_o == m; nothing is allocated before it.
+//     3. launch_remode_split_compact and launch_dict_build on the part's new storage.
+//   join (partitioned -> replicated):
+//     1. every part's rows at every window cut (launch_node_save_bounds), one launch
+//        and one copy back per part; the one mid-way wait; the slices' verdict, which
+//        bounds every copy below.
+//     2. replica j, on a storage for all m rows: per window the other parts' slices
+//        are peer-copied into one of two staging windows on a copy stream while the
+//        main stream scatters j's own slice and the window before; then the bitmap's
+//        count, the counters' copy back and launch_dict_build over the m rows.
+//     3. the verdict after the last wait; a refusal frees everything.
+//   same mode: ngpu_node_dict_retire_parts' compacting copy (n == 0) with the
+//   exchange the target asks for.
+// Nothing of base's storages is written; every stream is waited for on every path.
+
+// The node handle's storage of a remode: base's placement rows (if it keeps any)
+// with a fork's room.
+int remode_place(PartsCall &c, DictStorage **hst) {
+  const uint64_t cap = remode_caps(c.m).rec_cap;
+  if (int rc = storage_alloc_place_only(c.e0, c.rows && c.m ? cap : 0, hst)) return rc;
+  (*hst)->rec_cap = cap;
+  (*hst)->used = c.m;
+  if (c.rows && c.m) memcpy((*hst)->place, c.rows, c.m * sizeof(DictPlace));
+  return 0;
+}
+
+// The handle over the parts' new storages (pt[o].dst, s[o] rows each), handed over.
+ngpu_dict *remode_handle(PartsCall &c, const std::vector<uint64_t> &s, DictStorage *hst, bool replicated,
+                         bool routed) {
+  ngpu_dict *d = dict_derive(c.base);
+  d->replicated = replicated;
+  d->routed = routed;
+  d->dev.m = c.m;
+  d->dev.n_blobs = c.nb0;
+  d->st = hst;
+  d->has_place = c.rows && c.m;
+  for (uint32_t o = 0; o < c.W; ++o) {
+    ngpu_dict *p = dict_derive(c.base->parts[o]);
+    p->st = c.pt[o].dst;
+    c.pt[o].dst = nullptr;
+    dict_bind(p, s[o], c.nb0);
+    d->parts.push_back(p);
+  }
+  d->blob_table = c.base->blob_table;
+  return d;
+}
+
+NodeRetireScratch remode_scratch_bytes(uint64_t bytes) {  // (PartsCall allocates lay.bytes)
+  NodeRetireScratch r;
+  r.bytes = bytes;
+  return r;
+}
+
+int node_dict_split(ngpu_node *node, ngpu_dict *base, bool routed, ngpu_dict **out) {
+  PartsCall c(node, base, "node dict remode", "node_dict_remode");
+  ngpu_engine *e0 = c.e0;
+  const uint32_t W = c.W;
+  const uint64_t m = c.m;
+  for (uint32_t o = 0; o < W; ++o)
+    if (base->parts[o]->dev.m != m)
+      return fail(e0, NGPU_EINVAL, "node dict remode: replica %u of %llu entries, dict of %llu", o,
+                  (unsigned long long)base->parts[o]->dev.m, (unsigned long long)m);
+  if (int rc = c.pinned()) return rc;
+  const RemodeSplitScratch lay = remode_split_scratch_layout(m);
+
+  // 1. every part's keep words, prefixes and s_o
+  for (uint32_t o = 0; o < W && !c.rc; ++o) {
+    const ngpu_dict *bp = base->parts[o];
+    DeviceGuard dg(node->dev[o]);
+    if (!c.part_begin(o, remode_scratch_bytes(lay.bytes), 4)) break;
+    RetirePart &p = c.pt[o];
+    const hipStream_t s = p.bs->s;
+    c.mark(p, 0);
+    launch_remode_split_keep_scan(bp->st ? bp->st->rec : nullptr, m, W, o, (uint64_t *)(p.scr + lay.words),
+                                  (uint32_t *)(p.scr + lay.cnt), (uint64_t *)(p.scr + lay.sums), s);
+    c.mark(p, 1);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(node->eng[o]->fold_h, p.scr + remode_split_total_at(lay, m), 8, hipMemcpyDeviceToHost,
+                       s) != hipSuccess)
+      c.rc = fail(e0, NGPU_EHIP, "node dict remode: part %u: keep scan failed", o);
+  }
+  c.stamp(0);
+  c.quiesce();  // the call's only mid-way wait
+  c.stamp(1);
+  // 2. the verdict; nothing is allocated before it
+  std::vector<uint64_t> s_o(W, 0);
+  if (!c.rc) {
+    for (uint32_t o = 0; o < W; ++o) s_o[o] = node->eng[o]->fold_h[0];
+    const RemodeVerdict v = remode_split_verdict(W, s_o.data(), m);
+    if (!v.ok())
+      c.rc = fail(e0, NGPU_EINVAL, "node dict remode: %s (%llu of %llu)", remode_refusal(v.refusal),
+                  (unsigned long long)v.got, (unsigned long long)v.want);
+  }
+  if (c.rc) {
+    c.release();
+    return c.rc;
+  }
+  // 3. every part's rows onto a storage of its own, and its table
+  for (uint32_t o = 0; o < W && !c.rc; ++o) {
+    RetirePart &p = c.pt[o];
+    const ngpu_dict *bp = base->parts[o];
+    DeviceGuard dg(node->dev[o]);
+    const RemodeCaps caps = remode_caps(s_o[o]);
+    if ((c.rc = storage_alloc(node->eng[o], caps.rec_cap, caps.table_cap, false, &p.dst))) {
+      c.rc = fail(e0, c.rc, "%s", ngpu_last_error(node->eng[o]));
+      break;
+    }
+    p.dst->used = s_o[o];
+    const hipStream_t s = p.bs->s;
+    c.mark(p, 2);
+    launch_remode_split_compact(bp->st ? bp->st->rec : nullptr, m, (const uint64_t *)(p.scr + lay.words),
+                                (const uint32_t *)(p.scr + lay.cnt), p.dst->rec, s_o[o], s);
+    launch_dict_build(p.dst->rec, s_o[o], p.dst->table, p.dst->table_cap, s);
+    c.mark(p, 3);
+    if (hipGetLastError() != hipSuccess)
+      c.rc = fail(e0, NGPU_EHIP, "node dict remode: part %u: compaction failed", o);
+  }
+  c.stamp(2);
+  DictStorage *hst = nullptr;  // the node handle's rows, while the devices move the records
+  if (!c.rc) c.rc = remode_place(c, &hst);
+  c.quiesce();
+  c.stamp(3);
+  if (c.rc) {
+    storage_unref(hst);
+    c.release();
+    return c.rc;
+  }
+  if (c.trace)
+    for (uint32_t o = 0; o < W; ++o) {
+      const RetirePart &p = c.pt[o];
+      const double a = part_us(p, 0, 1), k = part_us(p, 2, 3);
+      if (a >= 0 && k >= 0)
+        fprintf(stderr,
+                "ngpu node_dict_remode split part=%u m=%llu s_o=%llu device_us=%.1f keep_scan_us=%.1f "
+                "compact_build_us=%.1f\n",
+                o, (unsigned long long)m, (unsigned long long)s_o[o], a + k, a, k);
+      (void)hipGetLastError();
+    }
+  ngpu_dict *d = remode_handle(c, s_o, hst, false, routed);
+  c.release();
+  c.stamp(4);
+  if (c.trace)
+    fprintf(stderr,
+            "ngpu node_dict_remode split host W=%u m=%llu enqueue_ms=%.3f wait_ms=%.3f alloc_launch_ms=%.3f "
+            "place_wait_ms=%.3f release_ms=%.3f\n",
+            W, (unsigned long long)m, c.t_host[0], c.t_host[1] - c.t_host[0], c.t_host[2] - c.t_host[1],
+            c.t_host[3] - c.t_host[2], c.t_host[4] - c.t_host[3]);
+  *out = d;
+  return 0;
+}
+
+// A replica's copy stream and the events of its two staging windows (join).
+struct JoinSide {
+  std::unique_ptr<BuildStream> cs;
+  hipEvent_t copied[2] = {}, scattered[2] = {};
+  bool used[2] = {false, false};
+};
+
+int node_dict_join(ngpu_node *node, ngpu_dict *base, uint64_t window_records, ngpu_dict **out) {
+  PartsCall c(node, base, "node dict remode", "node_dict_remode");
+  ngpu_engine *e0 = c.e0;
+  const uint32_t W = c.W;
+  const uint64_t m = c.m;
+  std::vector<uint64_t> m_o(W);
+  uint64_t total = 0;
+  for (uint32_t o = 0; o < W; ++o) total += m_o[o] = base->parts[o]->dev.m;
+  if (total != m)
+    return fail(e0, NGPU_EINVAL, "node dict remode: the parts hold %llu rows, the dict %llu entries",
+                (unsigned long long)total, (unsigned long long)m);
+  const uint64_t cw = remode_window_records(window_records, m), nw = remode_windows(m, cw);
+  if (int rc = c.pinned()) return rc;
+  static_assert(8 * kRemodeCtrWords <= 512, "the counters fit the engines' pinned words");
+  const RemodeJoinScratch lay = remode_join_scratch_layout(m, cw);
+  std::vector<std::vector<uint64_t>> off(W, std::vector<uint64_t>(nw + 1, 0));
+  std::vector<JoinSide> side(W);
+  auto rec_of = [&](uint32_t o) { return base->parts[o]->st ? base->parts[o]->st->rec : (const DictRec *)nullptr; };
+  auto quiesce = [&] {  // the copy streams too
+    c.quiesce();
+    for (uint32_t j = 0; j < W; ++j) {
+      if (!side[j].cs || !side[j].cs->s) continue;
+      DeviceGuard dg(node->dev[j]);
+      if (hipStreamSynchronize(side[j].cs->s) != hipSuccess && !c.rc)
+        c.rc = fail(e0, NGPU_EHIP, "node dict remode: replica %u: its copies failed", j);
+    }
+  };
+  auto release = [&] {  // after quiesce()
+    for (uint32_t j = 0; j < W; ++j) {
+      DeviceGuard dg(node->dev[j]);
+      for (int k = 0; k < 2; ++k) {
+        if (side[j].copied[k]) (void)hipEventDestroy(side[j].copied[k]);
+        if (side[j].scattered[k]) (void)hipEventDestroy(side[j].scattered[k]);
+      }
+      side[j].cs.reset();
+    }
+    c.release();
+  };
+
+  // 1. every part's rows at every cut
+  for (uint32_t o = 0; o < W && !c.rc; ++o) {
+    DeviceGuard dg(node->dev[o]);
+    if (!c.part_begin(o, remode_scratch_bytes(lay.bytes), 6)) break;
+    RetirePart &p = c.pt[o];
+    const hipStream_t s = p.bs->s;
+    c.mark(p, 0);
+    launch_node_save_bounds(rec_of(o), m_o[o], 0, m, cw, nw, (uint64_t *)(p.scr + lay.off), s);
+    c.mark(p, 1);
+    // (off's pageable memory: the stream is synchronised before it is read or freed)
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(off[o].data(), p.scr + lay.off, 8 * (nw + 1), hipMemcpyDeviceToHost, s) != hipSuccess)
+      c.rc = fail(e0, NGPU_EHIP, "node dict remode: part %u: the window cuts failed", o);
+  }
+  c.stamp(0);
+  c.quiesce();  // the call's only mid-way wait
+  c.stamp(1);
+  if (!c.rc) {  // no copy below leaves a part or overruns a staging window
+    const RemodeVerdict v = remode_join_slices(W, m, cw, off, m_o.data());
+    if (!v.ok())
+      c.rc = fail(e0, NGPU_EINVAL,
+                  "node dict remode: the parts do not tile the dict's ids (%s: part %u, window %llu, %llu of %llu)",
+                  remode_refusal(v.refusal), v.bad, (unsigned long long)v.window, (unsigned long long)v.got,
+                  (unsigned long long)v.want);
+  }
+  if (c.rc) {
+    release();
+    return c.rc;
+  }
+  // 2. every replica: its storage, the windows, the counters, its table
+  const RemodeCaps caps = remode_caps(m);
+  for (uint32_t j = 0; j < W && !c.rc; ++j) {
+    RetirePart &p = c.pt[j];
+    JoinSide &sd = side[j];
+    DeviceGuard dg(node->dev[j]);
+    if ((c.rc = storage_alloc(node->eng[j], caps.rec_cap, caps.table_cap, false, &p.dst))) {
+      c.rc = fail(e0, c.rc, "%s", ngpu_last_error(node->eng[j]));
+      break;
+    }
+    p.dst->used = m;
+    sd.cs.reset(new BuildStream(node->dev[j]));
+    bool ok = sd.cs->s != nullptr;
+    for (int k = 0; k < 2 && ok; ++k)
+      ok = hipEventCreateWithFlags(&sd.copied[k], hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&sd.scattered[k], hipEventDisableTiming) == hipSuccess;
+    const hipStream_t s = p.bs->s, cs = sd.cs->s;
+    uint64_t *d_bits = (uint64_t *)(p.scr + lay.bits), *d_ctr = (uint64_t *)(p.scr + lay.ctr);
+    // (the bitmap and the counters lie back to back)
+    ok = ok && hipMemsetAsync(d_bits, 0, lay.off - lay.bits, s) == hipSuccess;
+    c.mark(p, 2);
+    for (uint64_t t = 0; t < nw && ok; ++t) {
+      const int slot = (int)(t & 1);
+      const uint64_t a = remode_cut(m, cw, t), n = remode_cut(m, cw, t + 1) - a;
+      DictRec *stage = (DictRec *)(p.scr + lay.stage[slot]);
+      uint64_t staged = 0;
+      for (uint32_t q = 0; q < W && ok; ++q) {
+        const uint64_t cnt = off[q][t + 1] - off[q][t];
+        if (q == j || !cnt) continue;
+        // the window before last has left this staging window
+        if (!staged && sd.used[slot]) ok = hipStreamWaitEvent(cs, sd.scattered[slot], 0) == hipSuccess;
+        ok = ok && hipMemcpyPeerAsync(stage + staged, node->dev[j], rec_of(q) + off[q][t], node->dev[q],
+                                      cnt * sizeof(DictRec), cs) == hipSuccess;
+        staged += cnt;  // (<= n <= cw: remode_join_slices)
+      }
+      if (staged) ok = ok && hipEventRecord(sd.copied[slot], cs) == hipSuccess;
+      // j's own slice is read where it lies, while the copies run
+      const uint64_t own = off[j][t + 1] - off[j][t];
+      if (ok && own) launch_remode_join_scatter(rec_of(j) + off[j][t], own, a, n, m, p.dst->rec, d_bits, d_ctr, s);
+      if (ok && staged) {
+        ok = hipStreamWaitEvent(s, sd.copied[slot], 0) == hipSuccess;
+        if (ok) launch_remode_join_scatter(stage, staged, a, n, m, p.dst->rec, d_bits, d_ctr, s);
+        ok = ok && hipEventRecord(sd.scattered[slot], s) == hipSuccess;
+        sd.used[slot] = true;
+      }
+    }
+    if (ok) {
+      launch_remode_bitmap_count(d_bits, m, d_ctr, s);
+      c.mark(p, 3);
+      ok = hipGetLastError() == hipSuccess &&
+           hipMemcpyAsync(node->eng[j]->fold_h, d_ctr, 8 * kRemodeCtrWords, hipMemcpyDeviceToHost, s) == hipSuccess;
+    }
+    if (ok) {
+      // (a refused call builds over rows never written: the table is bounded by its
+      // capacity whatever they hold, and it is freed with the storage)
+      c.mark(p, 4);
+      launch_dict_build(p.dst->rec, m, p.dst->table, p.dst->table_cap, s);
+      c.mark(p, 5);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    if (!ok) {
+      (void)hipGetLastError();
+      c.rc = fail(e0, NGPU_EHIP, "node dict remode: replica %u: moving its rows failed", j);
+    }
+  }
+  c.stamp(2);
+  DictStorage *hst = nullptr;  // the node handle's rows, while the devices move the records
+  if (!c.rc) c.rc = remode_place(c, &hst);
+  quiesce();
+  c.stamp(3);
+  // 3. the verdict
+  if (!c.rc) {
+    std::vector<uint64_t> h_ctr((size_t)W * kRemodeCtrWords);
+    for (uint32_t j = 0; j < W; ++j)
+      memcpy(&h_ctr[(size_t)j * kRemodeCtrWords], node->eng[j]->fold_h, 8 * kRemodeCtrWords);
+    const RemodeVerdict v = remode_join_verdict(W, h_ctr.data(), m);
+    if (!v.ok())
+      c.rc = fail(e0, NGPU_EINVAL,
+                  "node dict remode: the parts do not tile the dict's ids (%s: replica %u, %llu, %llu entries)",
+                  remode_refusal(v.refusal), v.bad, (unsigned long long)v.got, (unsigned long long)m);
+  }
+  if (c.rc) {
+    storage_unref(hst);
+    release();
+    return c.rc;
+  }
+  if (c.trace)
+    for (uint32_t o = 0; o < W; ++o) {
+      const RetirePart &p = c.pt[o];
+      const double a = part_us(p, 0, 1), b = part_us(p, 2, 3), k = part_us(p, 4, 5);
+      if (a >= 0 && b >= 0 && k >= 0)
+        fprintf(stderr,
+                "ngpu node_dict_remode join part=%u m=%llu m_o=%llu windows=%llu device_us=%.1f bounds_us=%.1f "
+                "copy_scatter_us=%.1f build_us=%.1f\n",
+                o, (unsigned long long)m, (unsigned long long)m_o[o], (unsigned long long)nw, a + b + k, a, b, k);
+      (void)hipGetLastError();
+    }
+  ngpu_dict *d = remode_handle(c, std::vector<uint64_t>(W, m), hst, true, false);
+  release();
+  c.stamp(4);
+  if (c.trace)
+    fprintf(stderr,
+            "ngpu node_dict_remode join host W=%u m=%llu enqueue_ms=%.3f wait_ms=%.3f alloc_launch_ms=%.3f "
+            "place_wait_ms=%.3f release_ms=%.3f\n",
+            W, (unsigned long long)m, c.t_host[0], c.t_host[1] - c.t_host[0], c.t_host[2] - c.t_host[1],
+            c.t_host[3] - c.t_host[2], c.t_host[4] - c.t_host[3]);
+  *out = d;
+  return 0;
+}
+
+int node_dict_remode(ngpu_node *node, ngpu_dict *base, uint32_t mode, uint64_t window_records,
+                     ngpu_dict **out) {
+  bool replicated = false, routed = false;
+  if (int rc = node_dict_mode(node, mode, &replicated, &routed)) return rc;
+  if (base->parts.empty())
+    return fail(node->eng[0], NGPU_EINVAL, "node dict remode: not a node dict (a plain dict has no mode)");
+  if (int rc = node_dict_base_check(node, base, "remode")) return rc;
+  if (replicated == base->replicated) {  // the compacting copy, with the exchange asked for
+    ngpu_dict *d = nullptr;
+    if (int rc = node_dict_retire_parts(node, base, nullptr, 0, &d)) return rc;
+    d->routed = routed;
+    *out = d;
+    return 0;
+  }
+  return replicated ? node_dict_join(node, base, window_records, out)
+                    : node_dict_split(node, base, routed, out);
 }
 
 // ngpu_node_dict_export of a partitioned dict: every part's HBM rows come back in
@@ -1733,6 +2109,34 @@ int ngpu_node_dict_distill_parts(ngpu_node *node, ngpu_dict *base, uint32_t min_
     if (!rc && info) *info = got;
     return rc;
   });
+}
+
+static_assert(sizeof(ngpu_node_dict_remode_options) == 16, "ngpu_node_dict_remode_options is 16 bytes");
+static_assert(sizeof(ngpu_node_dict_info) == 528, "ngpu_node_dict_info is 528 bytes");
+
+int ngpu_node_dict_remode(ngpu_node *node, ngpu_dict *base, uint32_t mode,
+                          const ngpu_node_dict_remode_options *opt, ngpu_dict **out) {
+  if (out) *out = nullptr;
+  if (!node || !base || !out || (opt && (opt->flags || opt->reserved))) return NGPU_EINVAL;
+  const uint64_t window_records = opt ? opt->window_records : 0;
+  const int rc = guarded([&] { return node_dict_remode(node, base, mode, window_records, out); });
+  if (rc) *out = nullptr;
+  return rc;
+}
+
+int ngpu_node_dict_info_get(const ngpu_node *node, const ngpu_dict *d, ngpu_node_dict_info *out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!node || !d || !out) return NGPU_EINVAL;
+  if (d->parts.empty())
+    return fail(node->eng[0], NGPU_EINVAL, "node dict info: not a node dict (ngpu_dict_info_get takes it)");
+  if (int rc = node_dict_base_check(const_cast<ngpu_node *>(node), d, "info")) return rc;
+  out->mode = d->replicated ? NGPU_NODE_DICT_REPLICATE
+                            : NGPU_NODE_DICT_PARTITION |
+                                  (d->routed ? NGPU_NODE_EXCHANGE_ROUTED : NGPU_NODE_EXCHANGE_COPY);
+  out->parts = (uint32_t)d->parts.size();
+  out->entries = d->dev.m;
+  for (size_t i = 0; i < d->parts.size() && i < 64; ++i) out->part_entries[i] = d->parts[i]->dev.m;
+  return 0;
 }
 
 int ngpu_node_dict_export(ngpu_node *node, const ngpu_dict *d, void *records, uint64_t cap,

@@ -98,7 +98,9 @@ EXPORTS = ["ngpu_abi_version", "ngpu_create", "ngpu_destroy", "ngpu_last_error",
            # dict distill (additive in ABI 7)
            "ngpu_dict_distill", "ngpu_node_dict_distill",
            # node dict distill across parts (additive in ABI 7)
-           "ngpu_node_dict_distill_parts"]
+           "ngpu_node_dict_distill_parts",
+           # node dict remode (additive in ABI 7)
+           "ngpu_node_dict_remode", "ngpu_node_dict_info_get"]
 
 # ngpu_dict_place: the compressed placement of one folded record (host rows)
 DICT_PLACE_DTYPE = np.dtype([("compressed_offset", "<u8"), ("compressed_size", "<u4"), ("flags", "<u4")])
@@ -110,6 +112,22 @@ class NgpuDictInfo(ctypes.Structure):
                 ("shares_base_storage", ctypes.c_uint32), ("has_blob_table", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32 * 2)]
 
+
+class NgpuNodeDictRemodeOptions(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("window_records", ctypes.c_uint64)]
+
+
+class NgpuNodeDictInfo(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_uint32), ("parts", ctypes.c_uint32), ("entries", ctypes.c_uint64),
+                ("part_entries", ctypes.c_uint64 * 64)]
+
+    def as_dict(self) -> dict:
+        return {"mode": int(self.mode), "parts": int(self.parts), "entries": int(self.entries),
+                "part_entries": [int(x) for x in self.part_entries]}
+
+
+assert ctypes.sizeof(NgpuNodeDictRemodeOptions) == 16 and ctypes.sizeof(NgpuNodeDictInfo) == 528
 
 DICT_SAVE_NO_BLOB_TABLE = 0x1
 
@@ -405,6 +423,9 @@ def lib():
     L.ngpu_node_dict_distill.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(NgpuDictDistillInfo)]
     L.ngpu_node_dict_distill_parts.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp),
                                                ctypes.POINTER(NgpuDictDistillInfo)]
+    L.ngpu_node_dict_remode.argtypes = [vp, vp, u32, ctypes.POINTER(NgpuNodeDictRemodeOptions),
+                                        ctypes.POINTER(vp)]
+    L.ngpu_node_dict_info_get.argtypes = [vp, vp, ctypes.POINTER(NgpuNodeDictInfo)]
     L.ngpu_dict_save_layout.argtypes = [u64, u32, ctypes.POINTER(NgpuDictSaveInfo)]
     L.ngpu_dict_save.argtypes = [vp, vp, ctypes.POINTER(NgpuDictSaveOptions), WRITE_FN, vp,
                                  ctypes.POINTER(NgpuDictSaveInfo)]
@@ -1728,6 +1749,25 @@ class Node:
         h, info = _dict_distill(lambda *a: lib().ngpu_node_dict_distill_parts(self._h, base._h, *a), self._err,
                                 "node_dict_distill_parts", min_refs, keep_blobs, merge_blob_ids, count_only)
         return (None if h is None else ChunkDict(h)), info
+
+    def dict_remode(self, base: ChunkDict, mode: int, *, window_records: int = 0) -> ChunkDict:
+        """ngpu_node_dict_remode: base's rows as a node dict of `mode` (the values
+        dict_create takes), moved on the GPUs: a replicated dict is split by owner
+        on every device, a partitioned one joined into a replica per device in
+        windows of window_records global ids (0: the library's default); the same
+        mode is a compacting copy with the exchange asked for.  base stays as it is."""
+        opt = NgpuNodeDictRemodeOptions(0, 0, int(window_records))
+        h = ctypes.c_void_p()
+        self._err(lib().ngpu_node_dict_remode(self._h, base._h, int(mode), ctypes.byref(opt), ctypes.byref(h)),
+                  "node_dict_remode")
+        return ChunkDict(h)
+
+    def dict_info(self, d: ChunkDict) -> dict:
+        """ngpu_node_dict_info_get: mode (with the exchange in use), parts, entries and
+        part_entries (the rows the handle sees on each part; all 64 words, 0 past W)."""
+        x = NgpuNodeDictInfo()
+        self._err(lib().ngpu_node_dict_info_get(self._h, d._h, ctypes.byref(x)), "node_dict_info_get")
+        return x.as_dict()
 
     def dict_export_parts(self, d: ChunkDict):
         """ngpu_node_dict_export: (records as rafs.CHUNK_INFO_DTYPE in global table
