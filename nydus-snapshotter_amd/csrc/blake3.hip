@@ -10,8 +10,8 @@
 //   * b3_groups<D>: one lane per aligned group of 2^D consecutive leaves of
 //     one nydus chunk.  The lane hashes its leaves (16 compressions each,
 //     64-B message blocks loaded straight into VGPRs with 16-B loads) and
-//     merges complete subtrees eagerly through a D-deep CV stack held in
-//     named registers, so the 2^D-1 parent compressions of its group are
+//     merges complete subtrees eagerly through a D-deep CV stack of its own
+//     in LDS, so the 2^D-1 parent compressions of its group are
 //     done at full lane occupancy.  Aligned groups are nodes of BLAKE3's
 //     left-complete tree, so their CVs are exact subtree CVs.  A chunk that
 //     fits one group (<= 2^D KiB) is finished in the lane (ROOT flag).
@@ -280,6 +280,32 @@ __global__ __launch_bounds__(kSmallPlanThreads) void b3_plan_small(
   }
 }
 
+// The eager merge stack of group_cv lives per lane in LDS: word i of entry l
+// of thread t at [l][i][t], so the 64 accesses of a wave to one word are 64
+// consecutive words (conflict-free), and an entry is addressed by the lane's
+// depth: nothing is shifted on a push or a pop.  (In 24 named registers the
+// stack was moved instead of indexed, 30-40 v_mov per leaf around the
+// whole-leaf loop, and b3_groups<3, 0> needed 107 VGPRs, 4 waves per SIMD;
+// now 80 and 6.  DESIGN.md section 3, "Occupancy under wave priority".)
+constexpr int kGroupThreads = 256;  // b3_groups' workgroup: one window of leaf groups
+// LDS words of b3_groups<D>: the lanes' stacks (D entries of 8 words each)
+// while the leaves are hashed; after the barrier that follows them the
+// in-window tree's two CV buffers and its parent lists, in the same storage.
+// D = 3: 24 KiB + 1.5 KiB of sort and counter words, six workgroups per CU.
+constexpr int kTreeWords = 2 * kGroupThreads * 8 + kGroupThreads;
+constexpr int groups_lds_words(int D) {
+  return D * 8 * kGroupThreads > kTreeWords ? D * 8 * kGroupThreads : kTreeWords;
+}
+// Waves per SIMD b3_groups<D, LM> is compiled for: 6 (80 VGPRs; measured
+// against 4 and 5 on C2, profiles/r9/ab_occupancy.json), min == max.  The
+// prefetching load modes hold a second message block and fit 96 VGPRs, not
+// 80, without scratch: 5.  D = 4's 32 KiB of stacks allow 4 workgroups per
+// CU.  D = 0 has no stack and keeps the compiler's own choice (79 VGPRs).
+constexpr int kGroupWaves = 6;
+constexpr int groups_waves(int D, int LM, bool most) {
+  return D == 0 ? (most ? 8 : 1) : D == 4 ? 4 : (LM == 2 || LM == 3) ? 5 : kGroupWaves;
+}
+
 // LM (load mode): bit0 = non-temporal loads, bit1 = prefetch the next 64-B
 // block of the lane's byte stream while the current one is compressed,
 // 5 = plain loads without the whole-leaf fast path (A/B reference).
@@ -294,7 +320,7 @@ template <int D, int LM>
 __device__ __forceinline__ int group_cv(const uint8_t *__restrict__ data, uint64_t data_len,
                                         const ngpu_chunk *__restrict__ chunks, uint32_t c,
                                         uint64_t ng, uint32_t j, uint64_t *__restrict__ err,
-                                        uint32_t cur[8]) {
+                                        uint32_t *lstk, uint32_t cur[8]) {
   constexpr int SD = D > 0 ? D : 1;
   const ngpu_chunk ch = chunks[c];
   const uint32_t len = ch.length;
@@ -316,33 +342,31 @@ __device__ __forceinline__ int group_cv(const uint8_t *__restrict__ data, uint64
   const uint8_t *end = data + data_len;
   if (PF) load_block<NT>(src + pos, min(64u, gend - pos), end, m);
 
-  uint32_t stk[SD][8];
-  uint32_t depth = 0;
   // Leaf k's CV is in cur: merge the complete subtrees it closes (eagerly,
   // through the D-deep stack), then push it unless it is the group's last.
+  // lstk: this lane's column of the workgroup's stack in LDS; entry l is its
+  // words lstk[(8 * l + i) * kGroupThreads].  depth <= SD: leaf k finds
+  // popcount(k) <= D entries, and ctz(k + 1) of them are its trailing ones;
+  // the guards below keep every index inside [0, SD) whatever cnt is.
+  uint32_t depth = 0;
   auto finish = [&](uint32_t k) {
     const bool last = (k + 1 == cnt);
     const uint32_t nm = last ? depth : (uint32_t)__builtin_ctz(k + 1);
-    for (uint32_t q = 0; q < nm; ++q) {
+    for (uint32_t q = 0; q < nm && depth > 0; ++q) {
       uint32_t pm[16];
+      // the pop comes before compress(): nothing between its raise and its drop
+      const uint32_t *top = lstk + (depth - 1) * (8 * kGroupThreads);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) { pm[i] = stk[0][i]; pm[8 + i] = cur[i]; }
+      for (int i = 0; i < 8; ++i) { pm[i] = top[i * kGroupThreads]; pm[8 + i] = cur[i]; }
+      --depth;
       const uint32_t flags = PARENT | ((last && root_group && q + 1 == nm) ? ROOT : 0);
       set_iv(cur);
       compress(cur, pm, 0, 64, flags);
-#pragma unroll
-      for (int l = 0; l + 1 < SD; ++l)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) stk[l][i] = stk[l + 1][i];
-      --depth;
     }
-    if (!last) {
+    if (!last && depth < (uint32_t)SD) {
+      uint32_t *top = lstk + depth * (8 * kGroupThreads);
 #pragma unroll
-      for (int l = SD - 1; l > 0; --l)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) stk[l][i] = stk[l - 1][i];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) stk[0][i] = cur[i];
+      for (int i = 0; i < 8; ++i) top[i * kGroupThreads] = cur[i];
       ++depth;
     }
   };
@@ -425,13 +449,16 @@ __device__ __forceinline__ uint32_t group_work(uint32_t len, uint32_t j) {
 }
 
 // In-window tree levels by lane quads (defined with compress_quad below).
-__device__ __forceinline__ void wg_tree_quad(uint32_t *b0, uint32_t *b1, uint32_t *nit, bool inwg,
+__device__ __forceinline__ void wg_tree_quad(uint32_t *b0, uint32_t *b1, uint32_t *item,
+                                             uint32_t *item_c, uint32_t *nit, bool inwg,
                                              uint32_t k, uint32_t j, uint32_t o, uint32_t c,
                                              const uint32_t cur[8], uint32_t slot,
                                              ngpu_result *__restrict__ out);
 
 template <int D, int LM>
-__global__ __launch_bounds__(256) void b3_groups(
+__global__ __launch_bounds__(kGroupThreads)
+__attribute__((amdgpu_waves_per_eu(groups_waves(D, LM, false), groups_waves(D, LM, true))))
+void b3_groups(
     const uint8_t *__restrict__ data, uint64_t data_len,
     const ngpu_chunk *__restrict__ chunks, uint64_t n,
     const uint64_t *__restrict__ gbase, const uint32_t *__restrict__ gchunk,
@@ -439,8 +466,11 @@ __global__ __launch_bounds__(256) void b3_groups(
     ngpu_result *__restrict__ out, uint64_t *__restrict__ err,
     const uint32_t *__restrict__ small, const uint64_t *__restrict__ nsmall,
     uint32_t *__restrict__ tree_list) {
-  __shared__ uint32_t lcv[256 * 8];
-  __shared__ uint32_t lcv2[256 * 8];  // ping-pong partner of lcv
+  // the lanes' merge stacks, then (every stack is dead after the barrier
+  // behind the leaves) lcv and its ping-pong partner lcv2 and the tree's lists
+  __shared__ __attribute__((aligned(16))) uint32_t wlds[groups_lds_words(D)];
+  uint32_t *const lcv = wlds, *const lcv2 = wlds + kGroupThreads * 8;
+  uint32_t *const item = lcv2 + kGroupThreads * 8, *const item_c = item + kGroupThreads / 2;
   // groups [0, gm): multi-group chunks in chunk order; [gm, gm + ns): the
   // single-group chunks, largest first
   const uint64_t gm = gbase[n];
@@ -511,7 +541,7 @@ __global__ __launch_bounds__(256) void b3_groups(
       base = g;
       ng = 1;
     }
-    st = group_cv<D, LM>(data, data_len, chunks, c, ng, j, err, cur);
+    st = group_cv<D, LM>(data, data_len, chunks, c, ng, j, err, wlds + threadIdx.x, cur);
   }
   if (st == 1) {
     uint4 *d = reinterpret_cast<uint4 *>(out[c].digest);
@@ -537,7 +567,7 @@ __global__ __launch_bounds__(256) void b3_groups(
   if (!__syncthreads_or(inwg)) return;
   const uint32_t o = (uint32_t)(base - g0);  // chunk's first slot in lcv
   uint32_t k = inwg ? (uint32_t)ng : 1;
-  wg_tree_quad(lcv, lcv2, nit, inwg, k, j, o, c, cur, slot, out);
+  wg_tree_quad(lcv, lcv2, item, item_c, nit, inwg, k, j, o, c, cur, slot, out);
 }
 
 // Upper levels: one workgroup per chunk with more than one leaf group.
@@ -634,11 +664,12 @@ constexpr QuadSched kQuadSched = make_quad_sched();
 // groups per workgroup) 14 wave-compressions for 3.97 of parent work, about
 // 2.7 % of the kernel's issued VALU.  The chunk's own lanes (slot o + j,
 // group j of k) list the level's parents and promote an odd tail.
-__device__ __forceinline__ void wg_tree_quad(uint32_t *b0, uint32_t *b1, uint32_t *nit, bool inwg,
+__device__ __forceinline__ void wg_tree_quad(uint32_t *b0, uint32_t *b1, uint32_t *item,
+                                             uint32_t *item_c, uint32_t *nit, bool inwg,
                                              uint32_t k, uint32_t j, uint32_t o, uint32_t c,
                                              const uint32_t cur[8], uint32_t slot,
                                              ngpu_result *__restrict__ out) {
-  __shared__ uint32_t item[128], item_c[128];  // <= 128 parents per level (256 slots)
+  // item, item_c: <= 128 parents per level (256 slots)
   const uint32_t q = threadIdx.x & 3, quad = threadIdx.x >> 2;
   if (inwg) {
 #pragma unroll

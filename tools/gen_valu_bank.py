@@ -129,7 +129,21 @@ def streams(compiled_s=None):
         v["compiled_raw_prio_c"] = prio_flips(raw, slow=1, fast=0, min_run=8)  # 8-long runs only
         # no flips: every other wave of a SIMD at priority 1 for the whole loop
         v["compiled_raw_prio_static"] = list(raw)
+        # compiled_raw and its winner with the registers renumbered downwards,
+        # each kept in its bank (N mod 4): the stream names v0..v72, which caps
+        # it at 6 waves per SIMD; packed it fits 8
+        v["compiled_raw_lo"] = pack_regs(raw)
+        v["compiled_raw_prio_a_lo"] = pack_regs(v["compiled_raw_prio_a"])
     return v
+
+
+def pack_regs(ops):
+    """`ops` with every VGPR renamed to the lowest free one of its own bank."""
+    to, used = {}, [0, 0, 0, 0]
+    for r in regs(ops):
+        to[r] = r % 4 + 4 * used[r % 4]
+        used[r % 4] += 1
+    return [re.sub(r"\bv(\d+)\b", lambda m: f"v{to[int(m.group(1))]}", o) for o in ops]
 
 
 STATIC_PRIO = ("compiled_raw_prio_static",)
@@ -341,8 +355,13 @@ int main(int argc, char **argv) {
   uint64_t *h = (uint64_t *)malloc(maxw * 32);
   for (const V &v : kV) {
     if (argc > 1 && strcmp(argv[1], "all") && !strstr(v.name, argv[1])) continue;
+    // waves per SIMD the kernel's own register count allows (the named VGPRs
+    // plus the compiler's, allocated in eights out of 512)
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v.k, threads, 0) != hipSuccess) return 4;
+    const int max_w = per_cu * (threads / 64) / 4;
     for (int w : {1, 2, 3, 4, 5, 6, 8}) {
-      if (w * ((v.regs + 16 + 7) / 8 * 8) > 512) continue;  // cannot hold w waves per SIMD
+      if (w > max_w) continue;  // cannot hold w waves per SIMD
       if ((simds * w * rounds) % (threads / 64)) continue;
       run(v, w, threads, rounds, d, h, simds);
     }

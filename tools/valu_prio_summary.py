@@ -15,7 +15,9 @@ WHAT = {"compiled_raw": "the kernel's G stream with the compiler's pads, no s_se
         "compiled_raw_prio_a": "priority 1 on the 4-cycle runs, 0 on the 2-cycle runs",
         "compiled_raw_prio_b": "priority 0 on the 4-cycle runs, 1 on the 2-cycle runs",
         "compiled_raw_prio_c": "flips at the runs of 8 only: 0 on the 8-long 2-cycle runs, 1 elsewhere",
-        "compiled_raw_prio_static": "no flips: every other wave of a SIMD at priority 1 for the whole loop"}
+        "compiled_raw_prio_static": "no flips: every other wave of a SIMD at priority 1 for the whole loop",
+        "compiled_raw_lo": "compiled_raw with its registers packed downwards inside their banks (fits 8 waves)",
+        "compiled_raw_prio_a_lo": "compiled_raw_prio_a with its registers packed the same way"}
 
 
 def screen(path):
